@@ -9,10 +9,17 @@ Workload (BASELINE.json configs[1], metric quoted on it):
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 the driver
 uses torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE from the env).
-Rank 0 prints ONE JSON line (see README / DESIGN.md §Measurement).  A default
-N=1 run (CPU leg on) also runs BASELINE configs[2] -- the UNetResNet VAE step,
-same steps / warmup -- as a child process and nests its line under
-"secondary.config3_vae"; the headline value is config 2's.
+Rank 0 prints ONE JSON line (see README / DESIGN.md §Measurement).
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K
+timed steps, the --dump-outputs files when asked for, the JSON line (its
+"roofline", "cpu_baseline" and "parity" are null).  --full adds the legs
+that take runs of their own: the per-launch roofline of the 3x3 kernels, the
+CPU oracle baseline with the fp32 parity check, and (N=1, UNet, CPU leg on)
+BASELINE configs[2] -- the UNetResNet VAE step, same steps / warmup -- as a
+child process whose line is nested under "secondary.config3_vae"; the
+headline value is config 2's.  --no-roofline / --no-cpu-baseline /
+--no-secondary drop single legs of a --full run.
 """
 import argparse
 import json
@@ -73,7 +80,7 @@ def parse():
                     help="print the roofline leg's per-launch GEMM table (shape, kernel, time) to stderr")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the config-3 (VAE) secondary line that a default N=1 UNet run appends "
+                    help="skip the config-3 (VAE) secondary line that a --full N=1 UNet run appends "
                          "(--no-cpu-baseline, the A/B and profiling runs, skips it too)")
     ap.add_argument("--cpu-batch", type=int, default=8, help="CPU baseline batch (BASELINE.md §4: 8)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU steps per leg after 1 warmup")
@@ -96,7 +103,38 @@ def parse():
                     help="replay the step as one captured HIP graph (vaeunet_amd.graph); auto = on "
                          "at world size 1 with the fused optimizer; at N > 1 only with 'on' (the captured "
                          "RCCL all-reduces are untested across GPUs: experimental)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: roofline, CPU baseline + parity, "
+                         "config-3 (VAE) secondary (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left its caller (loss, gradient "
+                         "norm, updated parameters) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_PARAM_SAMPLE = 4 << 20   # elements of the flat parameter vector kept (16 MB of float32)
+
+
+def dump_outputs(path, model, loss, grad_norm):
+    """What a caller of the timed step holds after its last call, as
+    ``path/<name>.npy``: the loss it returned (float32), the total gradient
+    norm of that step when the step exposes it (the graph replay does), and
+    the parameters it updated in place -- the L2 norm of every parameter in
+    ``named_parameters()`` order (float64) and a fixed, seeded sample of the
+    flat float32 parameter vector (all of it when it is small enough)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    if grad_norm is not None:
+        np.save(os.path.join(path, "grad_norm.npy"), grad_norm.detach().float().reshape(-1).cpu().numpy())
+    ps = [p.detach().float().reshape(-1) for _, p in model.named_parameters()]
+    norms = torch.stack([p.double().norm() for p in ps])
+    np.save(os.path.join(path, "param_norms.npy"), norms.cpu().numpy())
+    flat = torch.cat(ps)
+    if flat.numel() > DUMP_PARAM_SAMPLE:
+        idx = torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0))
+        flat = flat[idx.sort().values.to(flat.device)]
+    np.save(os.path.join(path, "params.npy"), flat.cpu().numpy())
 
 
 def synthetic(B, S, C, rank, dev):
@@ -354,13 +392,13 @@ def gpu_parity(args, x, t, ref_out, ref_loss, dev, eps=None):
 def vae_secondary(args):
     """BASELINE configs[2] (UNetResNet VAE train step, same batch / image) as a
     child run of this script -- ``--model vae`` with the same steps / warmup,
-    its own 3x3 roofline, no CPU leg -- so the driver's default bench also
+    its own 3x3 roofline, no CPU leg -- so a --full bench also
     records config 3 (a child process, not an exec: this one has touched the
     GPU).  Its JSON line is nested as-is; the headline value stays config 2."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--model", "vae", "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--batch", str(args.batch), "--size", str(args.size),
-           "--no-cpu-baseline", "--graph", args.graph]
+           "--full", "--no-cpu-baseline", "--graph", args.graph]
     if args.no_roofline:
         cmd.append("--no-roofline")
     _progress("secondary: config-3 VAE run")
@@ -524,9 +562,12 @@ def main():
         dt = float(tt.item())
     ms = dt / args.steps * 1e3
     imgs = args.batch * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # before the further legs: the roofline leg runs two more steps
+        dump_outputs(args.dump_outputs, model, loss, graphed.grad_norm if graphed is not None else None)
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # live per-launch HIP-event timing of the 3x3 implicit-GEMM kernels over
         # 2 further steps (events on the launch stream, one pair per launch)
         K.TIMER = K.LaunchTimer(detail=args.layer_table, delay=args.timer_delay)
@@ -556,10 +597,10 @@ def main():
                                  "ms_per_step": round(v[1] / 2, 3)} for k, v in sorted(summ.items())}}
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, parity = cpu_baseline(args, dev)
     secondary = None
-    if rank == 0 and world == 1 and not vae and not (args.no_secondary or args.no_cpu_baseline):
+    if args.full and rank == 0 and world == 1 and not vae and not (args.no_secondary or args.no_cpu_baseline):
         secondary = {"config3_vae": vae_secondary(args)}
 
     if rank == 0:

@@ -11,8 +11,8 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$tag
 mkdir -p $O
 cd $R
-timeout -k 10 700 python -u bench.py > $O/bench_unet.log 2>&1 || { echo BENCH_FAIL; tail -20 $O/bench_unet.log; exit 1; }
-timeout -k 10 700 python -u bench.py --model vae > $O/bench_vae.log 2>&1 || { echo VAE_FAIL; tail -20 $O/bench_vae.log; exit 1; }
+timeout -k 10 700 python -u bench.py --full > $O/bench_unet.log 2>&1 || { echo BENCH_FAIL; tail -20 $O/bench_unet.log; exit 1; }
+timeout -k 10 700 python -u bench.py --full --model vae > $O/bench_vae.log 2>&1 || { echo VAE_FAIL; tail -20 $O/bench_vae.log; exit 1; }
 cd /tmp
 for m in unet vae; do
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$m -o p -- python -u $R/bench.py --model $m --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > $O/prof_$m.log 2>&1 || { echo PROF_FAIL $m; exit 1; }

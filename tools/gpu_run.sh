@@ -6,7 +6,7 @@
 # usage: bash tools/gpu_run.sh <tag> <step> [<step> ...]      -> gpurun_out/<tag>/
 # steps:
 #   tests[:<pytest -k or file list, comma separated>]  GPU tests (default: whole -m gpu suite)
-#   bench[:<model>]        the default bench line (model unet: CPU leg + config-3 secondary)
+#   bench[:<model>]        the bench line of a --full run (model unet: CPU leg + config-3 secondary)
 #   ab[:<model>[:<reps>]]  whole-tree A/B vs the tree copied to ab/tree (alternating, same box)
 #   flag:<module.NAME>[:<model>]  A/B of an engine flag (0 vs 1) on the current tree
 #   tune:<KEY>:<A>:<B>[:<model>]   A/B of a library tuning key (vu_gemm_set_tuning) A vs B
@@ -48,7 +48,7 @@ for step in "$@"; do
     bench)
       m=${arg:-unet}
       extra=""; [ "$m" != unet ] && extra="--model $m"
-      timeout -k 10 600 python -u bench.py $extra > $O/bench_$m.json 2> $O/bench_$m.err \
+      timeout -k 10 600 python -u bench.py --full $extra > $O/bench_$m.json 2> $O/bench_$m.err \
         || { echo "BENCH_FAIL $m"; tail -20 $O/bench_$m.err; exit 1; }
       tail -1 $O/bench_$m.json | cut -c1-240 ;;
     ab)

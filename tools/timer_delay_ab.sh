@@ -9,7 +9,7 @@ O=${GRAFT_REPO_ROOT:-$(pwd)}/gpurun_out/$tag
 mkdir -p $O
 for i in 1 2; do
   for dl in 0 $d; do
-    timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-secondary --steps 40 --timer-delay $dl \
+    timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-secondary --steps 40 --timer-delay $dl \
       > $O/b_${dl}_$i.json 2> $O/b_${dl}_$i.err || { echo "BENCH_FAIL delay $dl"; tail -5 $O/b_${dl}_$i.err; exit 1; }
     python - "$O/b_${dl}_$i.json" "$dl" <<'PY' | tee -a $O/summary.txt
 import json, sys
