@@ -656,6 +656,40 @@ int vu_dice_score(const float* x, const float* t, int64_t n, float epsilon,
                   float* score, double* counts, double* workspace,
                   void* stream);
 
+/* ---- validation metrics (utils/metrics.py, evaluate.py) ----------------- */
+/* counts[B][C][4] = exact (TP, FP, FN, TN) per (image, class) plane over the
+ * H x W mask pixels: pred = logit > 0.5f (the raw logit as fp32; NaN counts
+ * as false), truth = (float)mask > 0.5f.  logits [B, C, h, w]: ldtype 0 =
+ * fp32, 1 = bf16; mask [B, C, H, W]: mdtype 0 = fp32, 1 = uint8 / bool, 2 =
+ * int64; both are read in place through their four element strides (lstride,
+ * mstride: host arrays {batch, channel, row, column}; NCHW-contiguous and
+ * channels_last are the common cases, dense planes take a vector path).
+ * When (h, w) != (H, W), or resize != 0, the logit at a mask pixel is the
+ * bilinear interpolation of the logits by the source-index rules of
+ * F.interpolate(mode='bilinear', align_corners), formed in fp32 registers;
+ * the resized tensor is never written.  accumulate != 0 adds into counts
+ * instead of storing.  hard (optional): uint8 [B, C, H, W] contiguous, the
+ * hard prediction at mask resolution.  Limits: H * W < 2^31, B * C <= 65535.
+ * workspace: vu_seg_counts_workspace_bytes(B * C). */
+int64_t vu_seg_counts_workspace_bytes(int64_t planes);
+int vu_seg_counts(const void* logits, int ldtype, const int64_t* lstride, int h,
+                  int w, const void* mask, int mdtype, const int64_t* mstride,
+                  int B, int C, int H, int W, int align_corners, int resize,
+                  int64_t* counts, int accumulate, uint8_t* hard,
+                  void* workspace, void* stream);
+/* counts[P][4] (P = images x C planes, class fastest) -> out[P][6] (optional)
+ * = {dice, iou, precision, recall, specificity, accuracy} per plane, and
+ * pooled[6] (optional) = the same of all planes summed first, stored or, with
+ * pooled_accumulate, added to pooled[].  dice = 1 if 2TP+FP+FN == 0 else
+ * (2 TP + eps) / ((TP+FP) + (TP+FN) + eps) in vu_dice_score's fp32
+ * arithmetic; iou = (TP+eps)/(TP+FP+FN+eps), precision = (TP+eps)/(TP+FP+eps),
+ * recall = (TP+eps)/(TP+FN+eps), specificity = (TN+eps)/(TN+FP+eps), accuracy
+ * = (TP+TN)/(TP+FP+FN+TN), in fp64 from the integers and rounded once.
+ * class_total[C][4] (optional) += the counts of each class over the images. */
+int vu_seg_metrics(const int64_t* counts, int P, int C, double eps, float* out,
+                   float* pooled, int pooled_accumulate, int64_t* class_total,
+                   void* stream);
+
 /* ---- optimizer (train.py:334,406-411) ---------------------------------- */
 /* sum of squares of n fp32 values into out (fp64, deterministic) */
 int vu_sumsq(const float* x, int64_t n, double* out, double* workspace,

@@ -175,6 +175,10 @@ _SIGS = {
     "vu_kl_free_bits2": (_i, [_p, _p, _i, _i, _f, _p, _p, _p, _p, _p]),
     "vu_sumsq": (_i, [_p, _l, _p, _p, _p]),
     "vu_dice_score": (_i, [_p, _p, _l, _f, _p, _p, _p, _p]),
+    "vu_seg_counts_workspace_bytes": (_l, [_l]),
+    "vu_seg_counts": (_i, [_p, _i, C.POINTER(_l), _i, _i, _p, _i, C.POINTER(_l), _i, _i, _i, _i, _i, _i, _p, _i, _p,
+                           _p, _p]),
+    "vu_seg_metrics": (_i, [_p, _i, _i, C.c_double, _p, _p, _i, _p, _p]),
     "vu_mt_chunk_elems": (_l, []),
     "vu_mt_grad_norm": (_i, [_p, _i, _l, _f, _p, _p, _p, _p]),
     "vu_mt_scale_grads": (_i, [_p, _i, _l, _p, _p]),

@@ -1,0 +1,74 @@
+"""Validation loop (drop-in for the reference's evaluate.py, which train.py
+calls once per epoch): inference-mode forward, logits resized to the mask,
+all segmentation metrics -- with every per-batch result kept on the device.
+
+Per batch this runs the model and ``SegmentationMeter.update`` (one fused
+counts pass that resizes the logits on the fly, one small metrics launch);
+the host waits for the device once, when the epoch's numbers are read.
+
+Unpinned vs the reference (its evaluate.py was not available when this was
+written; both choices are arguments or return keys, so either reading is one
+line away):
+  * reduction: the plain keys are ``batch_mean`` -- the sum of the per-batch
+    pooled scores divided by the number of batches, the upstream U-Net
+    evaluate() convention; the scores of all validation pixels pooled are
+    returned too, under ``pooled_*``.
+  * ``align_corners=False`` for the logits -> mask resize: torch's default for
+    a bare ``F.interpolate(..., mode='bilinear')``.
+"""
+import torch
+
+from .metrics import METRIC_NAMES, SegmentationMeter
+
+CL = torch.channels_last
+
+
+def _split_batch(batch):
+    if isinstance(batch, dict):
+        return batch['image'], batch['mask']
+    image, mask = batch[0], batch[1]
+    return image, mask
+
+
+@torch.inference_mode()
+def evaluate(net, dataloader, device, amp=True, align_corners=False, max_batches=None):
+    """Validate ``net`` over ``dataloader``; returns a dict of Python floats:
+    ``dice, iou, precision, recall, specificity, accuracy`` (mean over batches
+    of the per-batch scores), the same under ``pooled_*`` (all pixels of the
+    run pooled) and ``batches``.
+
+    net: returns logits [B, C, h, w] or a tuple whose first item is the logits
+    (``(logits, mu, logvar)`` of the VAE U-Net).  Batches: ``{'image', 'mask'}``
+    dicts or ``(image, mask)`` pairs; a mask without a channel dimension
+    ([B, H, W]) gets one.  The logits are resized to the mask's resolution
+    inside the metric kernel when the two differ.  The net's training mode is
+    restored on return."""
+    device = torch.device(device)
+    was_training = net.training
+    net.eval()
+    meter = SegmentationMeter(align_corners=align_corners)
+    try:
+        for i, batch in enumerate(dataloader):
+            if max_batches is not None and i >= max_batches:
+                break
+            image, mask = _split_batch(batch)
+            image = image.to(device=device, dtype=torch.float32, non_blocking=True)
+            if image.dim() == 4:
+                image = image.contiguous(memory_format=CL)
+            mask = mask.to(device=device, non_blocking=True)
+            if mask.dim() == image.dim() - 1:
+                mask = mask.unsqueeze(1)
+            with torch.autocast(device.type, dtype=torch.bfloat16, enabled=bool(amp)):
+                out = net(image)
+            logits = out[0] if isinstance(out, (tuple, list)) else out
+            meter.update(logits, mask)
+    finally:
+        net.train(was_training)
+    if meter.batches == 0:
+        raise ValueError("evaluate: the dataloader produced no batch")
+    # one transfer (and the only host synchronisation) for all twelve numbers
+    both = torch.stack([meter.values("batch_mean"), meter.values("pooled")]).cpu()
+    res = {k: both[0, i].item() for i, k in enumerate(METRIC_NAMES)}
+    res.update({f"pooled_{k}": both[1, i].item() for i, k in enumerate(METRIC_NAMES)})
+    res["batches"] = meter.batches
+    return res

@@ -27,6 +27,8 @@ Reference ops each one replaces:
   attn_gate_fwd / _bwd           AttentionGate (train-mode BatchNorms)  unet_parts.py:7-30
   vae_bottleneck_fwd / _bwd      mu/logvar heads + reparameterize   unet_resnet.py:140-147,191-194
   bce_dice_loss                  CombinedLoss.forward             utils/loss.py:45-63
+  seg_counts                     F.interpolate + (x > 0.5) + the TP/FP/FN/TN sums of evaluate.py /
+                                 utils/metrics.py get_all_metrics (integer output, not differentiable)
 """
 import ctypes as C
 import types
@@ -35,6 +37,7 @@ import torch
 from . import _lib
 from . import engine as E
 from . import kernels as K
+from . import metrics as _metrics
 from ._lib import call, ptr, query, stream
 from .engine import conv_layout, convT_layout, w3x3_dgrad, w3x3_fwd, wT_dgrad, wT_fwd
 from .loss import _dense_pair
@@ -619,7 +622,25 @@ def _vb_backward(ctx, gmu, glv, gz, _gpooled):
 vae_bottleneck_fwd.register_autograd(_vb_backward, setup_context=_vb_setup)
 
 
+# ---- validation counts ---------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::seg_counts", mutates_args=(), device_types="cuda")
+def seg_counts(logits: torch.Tensor, masks: torch.Tensor, align_corners: bool = False) -> torch.Tensor:
+    """Exact (TP, FP, FN, TN) of logits > 0.5 vs masks > 0.5 per (image, class):
+    int64 [B, C, 4]; the logits are resized to the mask (bilinear) inside the
+    kernel when the resolutions differ (vaeunet_amd.metrics.seg_counts).  Not
+    differentiable (integer output)."""
+    return _metrics.seg_counts(logits, masks, align_corners)
+
+
+@seg_counts.register_fake
+def _(logits, masks, align_corners=False):
+    if logits.dim() != 4 or masks.dim() != 4 or logits.shape[:2] != masks.shape[:2]:
+        raise ValueError(f"vaeunet::seg_counts: logits {tuple(logits.shape)} and masks {tuple(masks.shape)} "
+                         "must be 4-d with equal batch and class sizes")
+    return torch.empty((logits.shape[0], logits.shape[1], 4), dtype=torch.int64, device=logits.device)
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
-       "bce_dice_loss")
+       "bce_dice_loss", "seg_counts")
