@@ -181,13 +181,11 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
 /*   VU_TUNE_GEN: highest kernel generation the GEMM dispatchers may pick
  *     (1 = generic only ... 4 = all, the default);
  *   VU_TUNE_SLAB4: 0 = scalar split-K slab reduce (default 1 = vectorised);
- *   VU_TUNE_V2_CFG: tile configuration of short-K v2 GEMMs (0 default, 1, 2);
  *   VU_TUNE_BN_NT_MB: streamed-tensor size (MB) from which the BatchNorm
  *     passes use non-temporal loads (default 32; -1 = never).
  * The library reads no environment variables: these are the only knobs. */
 #define VU_TUNE_GEN 12
 #define VU_TUNE_SLAB4 13
-#define VU_TUNE_V2_CFG 14
 #define VU_TUNE_BN_NT_MB 15
 /*   VU_TUNE_V7: small-grid 3x3 kernel (gemm_fwd7.hip): 0 = off (v4 split-K /
  *     v2 small-grid tiles), 1 = default (grids under one 256x256 tile per CU,
@@ -211,9 +209,8 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
  *     VU_TUNE_FP8_GRID caps the grid) */
 #define VU_TUNE_FP8_PP 21
 /*   VU_TUNE_ATTN: 1 (default) batched attention-gate kernels (U pixel rows /
- *     vectors of loads in flight per lane), 0 = one row per iteration,
- *     2 = as 1 with the psi backward that emits the BatchNorm partials on
- *     two rows per lane (fewer VGPRs, one more wave per SIMD) */
+ *     vectors of loads in flight per lane), 0 = one row per iteration; any
+ *     other value is refused */
 #define VU_TUNE_ATTN 22
 /*   VU_TUNE_FP8_C64: 1 (default) 64 -> 64 fp8 convs on the resident-weight
  *     tile-stream kernel (statistics row tile 64), 0 = the step-loop kernel */
@@ -225,10 +222,6 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
  *     small tensors (default 256; 0 = ~16 pixel rows per thread only).
  *     (Was 23 until round 4, the same key as VU_TUNE_FP8_C64, which took it.) */
 #define VU_TUNE_BN_MINBLK 25
-/*   VU_TUNE_W3_FAST: 1 (default) the halo weight-gradient main loop with
- *     immediate-offset fragment reads and incremental tile addressing, 0 the
- *     round-3 loop, 2 the round-4 loop without s_setprio (A/B runs) */
-#define VU_TUNE_W3_FAST 26
 /*   VU_TUNE_PP_FULL: 1 (default) = the ping-pong 3x3 kernel runs one read
  *     segment and one 32-MFMA segment per step (2 barriers) instead of two
  *     halves (0; bit-identical outputs) */
@@ -251,10 +244,6 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
  *     applies); 0 (default) = the two-launch path (the one-launch form
  *     measured 12 % slower on config 3: uncoalesced channel slices). */
 #define VU_TUNE_BN_ONEPASS 31
-/*   VU_TUNE_STREAM_PD: tiles of operand loads each wave of the 1x1 stream
- *     kernel (gemm_stream.hip) keeps in flight beyond the one it computes:
- *     1 or 2. */
-#define VU_TUNE_STREAM_PD 32
 /*   VU_TUNE_UNSAFE: 1 = allow the experiment modes (VU_TUNE_V6_XM,
  *     VU_TUNE_V7_XM, VU_TUNE_FP8_XM) to be set non-zero; several of them
  *     produce wrong results by design (timing decompositions).  Without it a
@@ -264,26 +253,9 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
  *     the two wave halves' epilogues staggered into the next tile's first
  *     group (bit-identical results), 0 = the round-5 lock-step kernel. */
 #define VU_TUNE_V6_STAG 34
-/*   VU_TUNE_BN_STATS1: 1 = vu_bn_finalize as one launch (the last block of
- *     each channel group combines the group's partials, handed off through
- *     write-through stores and one agent-scope atomic per block; measured
- *     0.6-1.1 % slower per step than the two launches), 0 (default) = the
- *     two-launch path (stage 1 + stage 2).  Same fp64 combine up to the
- *     summation order. */
-#define VU_TUNE_BN_STATS1 35
-/*   VU_TUNE_V5_GRP: 1 = the persistent short-K 1x1 / ConvT GEMM walks its
- *     tiles in 4 x 8 blocks per 32 consecutive tiles (one XCD's share of a
- *     round) when the tile grid divides that way, 0 (default) = row-major
- *     (the grouping measured 5-8 % slower on the up1 / up2 ConvT GEMMs:
- *     per XCD, sharing A across 16 column tiles beats the smaller set). */
-#define VU_TUNE_V5_GRP 36
-/*   VU_TUNE_V5_WIDE: 1 = the persistent short-K 1x1 / ConvT GEMM takes
- *     256 x 256 output tiles on 32-wide K steps (half the operand bytes per
- *     MFMA of the 256 x 128 tiles, the same 96 KB in flight) for problems with
- *     a full round of such tiles and no accumulate; 0 (default) = 256 x 128
- *     (the wide tiles measured 3-15 % slower per shape: each step fetches
- *     half cache lines of every operand row). */
-#define VU_TUNE_V5_WIDE 37
+/*   Keys 14, 26, 32, 35, 36, 37 are retired, refused
+ *     (hipErrorInvalidValue): measured-slower variants that were removed.
+ *     Do not reuse the numbers. */
 int vu_gemm_set_tuning(int key, int value);
 /* Bit mask of the experiment modes currently non-zero (bit 0 V6_XM, 1 V7_XM,
  * 2 FP8_XM): 0 in production.  bench.py refuses to report while it is not. */

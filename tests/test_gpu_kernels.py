@@ -237,6 +237,8 @@ def test_conv3x3_pingpong_kernel(case):
 
 TUNE_PP_FULL = 27
 TUNE_PP_PERSIST = 30
+TUNE_ATTN = 22
+TUNE_RETIRED = (14, 26, 32, 35, 36, 37)
 
 
 @pytest.mark.parametrize("case", [c for c in V4_CASES if c[4] % 128 == 0])
@@ -252,6 +254,19 @@ def test_conv3x3_pingpong_persistent(case, grid):
         _check_halo_conv(case, (128,))
     finally:
         _tune(*TUNE_DEFAULTS, (TUNE_PP_PERSIST, 0))
+
+
+def test_retired_tuning_keys_refused():
+    """The keys of the removed kernel variants (include/vaeunet.h, "retired,
+    refused") and VU_TUNE_ATTN values other than 0 / 1 are refused; a valid
+    value is still accepted afterwards.  No kernel launch."""
+    from vaeunet_amd import _lib
+    for key in TUNE_RETIRED:
+        with pytest.raises(RuntimeError, match="vu_gemm_set_tuning"):
+            _lib.call("vu_gemm_set_tuning", key, 1)
+    with pytest.raises(RuntimeError, match="vu_gemm_set_tuning"):
+        _lib.call("vu_gemm_set_tuning", TUNE_ATTN, 2)
+    assert _lib.call("vu_gemm_set_tuning", TUNE_ATTN, 1) == 0
 
 
 @pytest.mark.parametrize("case", [c for c in V4_CASES if c[4] % 128 == 0])
@@ -949,26 +964,14 @@ def test_batchnorm_train(mode, relu, shape):
     torch.testing.assert_close(bn_dev.bias.grad.cpu(), bn.bias.grad, rtol=2e-3, atol=1e-3)
 
 
-@pytest.mark.parametrize("stats1", [1, 0])
 @pytest.mark.parametrize("tiles,tile_rows,C", [(40000, 7, 64), (300, 128, 192), (5, 64, 8), (16385, 4, 16),
                                               (64, 128, 1024)])
-def test_bn_finalize_partials(tiles, tile_rows, C, stats1):
+def test_bn_finalize_partials(tiles, tile_rows, C):
     """vu_bn_finalize on synthetic per-tile (sum, M2) partials: several rounds
     per block (tiles > 64 x 256), several blocks and channel groups, a ragged
     last tile, an empty last block (16385 tiles); mean / biased var / running
-    stats vs an fp64 combination.  stats1: the one-launch finalize (the last
-    block of each channel group combines, VU_TUNE_BN_STATS1 = 1, opt-in) or
-    the two-launch path (default)."""
+    stats vs an fp64 combination."""
     K, _ = _k()
-    from vaeunet_amd import _lib as lib
-    lib.call("vu_gemm_set_tuning", 35, stats1)
-    try:
-        _bn_finalize_partials(K, tiles, tile_rows, C)
-    finally:
-        lib.call("vu_gemm_set_tuning", 35, 0)
-
-
-def _bn_finalize_partials(K, tiles, tile_rows, C):
     g = torch.Generator().manual_seed(41)
     rows = tiles * tile_rows - 3
     n = torch.full((tiles,), float(tile_rows), dtype=torch.float64)
@@ -995,7 +998,7 @@ def _bn_finalize_partials(K, tiles, tile_rows, C):
     torch.testing.assert_close(c[0], gamma.double() * invstd, rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(rv_d.cpu().double(), 0.9 + 0.1 * M2 / (n.sum() - 1), rtol=1e-5, atol=1e-6)
     assert int(nbt_d) == 1
-    # a second launch reuses the self-resetting arrival counters
+    # a second launch gives the same bits
     coef2 = K.bn_finalize(st, C, gamma.to(DEV), beta.to(DEV), None, None, None, 0.0, 1e-5)
     assert torch.equal(coef2[:, :].cpu(), coef.cpu())
 

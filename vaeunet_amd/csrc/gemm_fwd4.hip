@@ -1012,7 +1012,6 @@ int bn_tune(int key, int value);           // bn.hip
 int attn_tune(int key, int value);         // attention.hip
 extern int g_tune_gen;                     // gemm_fwd.hip
 extern int g_tune_slab4;                   // gemm_wgrad.hip
-extern int g_v2_cfg;                       // gemm_fwd2.hip
 
 namespace {
 int g_tune_unsafe = 0;  // VU_TUNE_UNSAFE
@@ -1069,11 +1068,6 @@ int set_tuning(int key, int value) {
   }
   if (key == VU_TUNE_SLAB4) {
     g_tune_slab4 = value;
-    return 0;
-  }
-  if (key == VU_TUNE_V2_CFG) {
-    if (value < 0 || value > 2) return (int)hipErrorInvalidValue;
-    g_v2_cfg = value;
     return 0;
   }
   if (conv_fp8_tune(key, value) == 0 || gemm_stream_tune(key, value) == 0 || gemm_fwd_v2_tune(key, value) == 0 ||

@@ -39,15 +39,6 @@ VU_DEV int fb(int row) { return (row & 3) | (((row >> (GS == 4 ? 4 : 3)) & 1) <<
 template <int GS>
 VU_DEV int swz_b(int row, int chunk) { return row * KB + ((chunk ^ fb<GS>(row)) << 4); }
 
-// 256-column tiles (round 6, VU_TUNE_V5_WIDE): 32-wide K steps, 64-byte LDS
-// rows.  ds_read_b128 serves 16-lane groups {0-3,12-15,20-27}, ...; a lane
-// reads row r16 = lane & 15 (+ a fragment base) at chunk lane >> 4, so the
-// physical chunk is the logical one XOR 2 * bit 2 of the row for A and XOR
-// 2 * bit 5 for B (whose fragment rows step by 32 every 4 lanes): every
-// group then hits 16 distinct 16-byte slots of a 256-byte bank window.
-VU_DEV int swz_aw(int row, int chunk) { return row * 64 + ((chunk ^ (((row >> 2) & 1) << 1)) << 4); }
-VU_DEV int swz_bw(int row, int chunk) { return row * 64 + ((chunk ^ (((row >> 5) & 1) << 1)) << 4); }
-
 template <int N>
 VU_DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -62,42 +53,21 @@ VU_DEV float hi_f(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
 struct Pix { int n, h, w; bool ok; };
 
-// Tile t of the walk -> (row tile, column tile).  grp (VU_TUNE_V5_GRP, round
-// 6): consecutive runs of 32 tiles -- the tiles one XCD's 32 CUs hold at a
-// time -- cover a 4 x 8 block of the tile grid instead of 2 x 16, when the
-// grid divides that way (per XCD: A of 4 row tiles + B of 8 column tiles
-// instead of 2 + 16, 4 instead of 5 MB at K = 1024).
-VU_DEV void v5_tile(int t, int ntiles, int grp, int& mt, int& nt) {
-  if (grp) {
-    const int g = t >> 5, i = t & 31, ngc = ntiles >> 3;
-    const int gr = g / ngc;
-    mt = gr * 4 + (i >> 3);
-    nt = (g - gr * ngc) * 8 + (i & 7);
-  } else {
-    mt = t / ntiles;
-    nt = t - mt * ntiles;
-  }
-}
-
 template <int BN, bool STATS, bool ACC, bool RELU = false>  // RELU: epilogue ReLU (VuGemmFwd.relu)
-__global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p, int grp) {
-  constexpr bool WD = BN == 256;        // round 6: 256 x 256 tiles on 32-wide K steps
-  static_assert(!(WD && ACC), "the wide tiles have no accumulate variant (registers)");
-  constexpr int KBY = WD ? 64 : KB;     // bytes of K per LDS row per step
-  constexpr int KST = KBY / 2;          // K elements per step
-  constexpr int CH = KBY / 16;          // 16-byte chunks per row
-  constexpr int RS = WD ? 2 : 3;        // log2(CH)
-  constexpr int NSW = WD ? 4 : NS;      // ring slots: NSW - 1 steps in flight (96 KB either way)
+__global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p) {
+  constexpr int KST = KB / 2;           // K elements per step
+  constexpr int CH = KB / 16;           // 16-byte chunks per row
+  constexpr int RS = 3;                 // log2(CH)
   constexpr int KK = KST / 32;          // MFMA k-slabs per step
-  constexpr int WNC = BN / WN;          // columns per wave: 128, 64 or 32
+  constexpr int WNC = BN / WN;          // columns per wave: 64 or 32
   constexpr int TM = BM / WM / 16;      // 4 pixel fragments per wave
-  constexpr int TN = WNC / 16;          // 8, 4 or 2 column fragments per wave
+  constexpr int TN = WNC / 16;          // 4 or 2 column fragments per wave
   constexpr int GS = TN;                // a lane owns 4*GS consecutive columns
   constexpr int CPL = GS / 2;           // 16-byte pieces per lane and pixel
   constexpr int LA = BM * CH / NT, LB = BN * CH / NT, NL = LA + LB;
   constexpr int NST = TM * CPL + (STATS ? 2 * TN : 0);  // vector stores per epilogue
-  constexpr int STAGE = (BM + BN) * KBY;
-  __shared__ __attribute__((aligned(16))) char smem[NSW * STAGE];
+  constexpr int STAGE = (BM + BN) * KB;
+  __shared__ __attribute__((aligned(16))) char smem[NS * STAGE];
 
   const VuGather& g = p.a;
   const int M = g.N * g.H * g.W;  // < 2^31 (host check)
@@ -128,24 +98,22 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p, int grp
   // k-steps its row pointers are resolved once and then advance by 64
   // channels per step (the per-step gather decode cost more VALU time than
   // the MFMAs of the step).
-  // row & 7 (row bit 2 for the wide tiles) is the same for all LA rows
-  const int lch_a = WD ? pchunk ^ (((tid >> 4) & 1) << 1) : pchunk ^ ((tid >> 3) & 7);
+  // row & 7 is the same for all LA rows
+  const int lch_a = pchunk ^ ((tid >> 3) & 7);
   int sg_t = lb, sg_kt = 0, seg_step = 0, seg_rem = 0;
   const bf16_t* ap[LA];
   const bf16_t* bp[LB];
   int lch_b[LB];
 #pragma unroll
-  for (int i = 0; i < LB; ++i)
-    lch_b[i] = WD ? pchunk ^ ((((i * NT + tid) >> 7) & 1) << 1) : pchunk ^ fb<GS>((i * NT + tid) >> 3);
+  for (int i = 0; i < LB; ++i) lch_b[i] = pchunk ^ fb<GS>((i * NT + tid) >> 3);
   Pix pa[LA];
   auto stage = [&](int slot) {
     const int k0 = sg_kt * KST;
     const int tap = k0 / g.C;
     const int cbase = k0 - tap * g.C;
     if (sg_kt == 0) {
-      int mt, ntl;
-      v5_tile(sg_t, ntiles, grp, mt, ntl);
-      const int n0 = ntl * BN;
+      const int mt = sg_t / ntiles;
+      const int n0 = (sg_t - mt * ntiles) * BN;
 #pragma unroll
       for (int i = 0; i < LA; ++i) {
         const int m = mt * BM + ((i * NT + tid) >> RS);
@@ -176,7 +144,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p, int grp
       seg_rem = g.cend[t] - cbase;
     }
     char* A = smem + slot * STAGE;
-    char* B = A + BM * KBY;
+    char* B = A + BM * KB;
     const int off = seg_step * KST;
     const bool cin = lch_a * 8 < seg_rem - off;  // channel tail of the source
 #pragma unroll
@@ -223,14 +191,12 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p, int grp
   int ct = lb, ckt = 0;  // tile / k-step being computed
   stage(0);
 #pragma unroll
-  for (int q = 1; q < NSW - 1; ++q)
+  for (int q = 1; q < NS - 1; ++q)
     if (S > q) stage(q);
   for (int s = 0; s < S; ++s) {
     const bool after_epi = s > 0 && ckt == 0;
     // steps issued after s that may stay in flight (and the last epilogue's stores)
-    if (NSW == 4 && s + 2 < S) {
-      if (after_epi) wait_vm<2 * NL + NST>(); else wait_vm<2 * NL>();
-    } else if (s + 1 < S) {
+    if (s + 1 < S) {
       if (after_epi) wait_vm<NL + NST>(); else wait_vm<NL>();
     } else {
       if (after_epi) wait_vm<NST>(); else wait_vm<0>();
@@ -238,9 +204,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p, int grp
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     const bool last = ckt == nk - 1;
-    int mt, ntl;
-    v5_tile(ct, ntiles, grp, mt, ntl);
-    const int m0 = mt * BM, n0 = ntl * BN;
+    const int mt = ct / ntiles;
+    const int m0 = mt * BM, n0 = (ct - mt * ntiles) * BN;
     const int col0 = n0 + wn * WNC + 4 * GS * gq;
     if (last) {
 #pragma unroll
@@ -252,21 +217,19 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p, int grp
         }
       }
     }
-    if (s + NSW - 1 < S) stage((s + NSW - 1) % NSW);
-    const char* A = smem + (s % NSW) * STAGE;
-    const char* B = A + BM * KBY;
+    if (s + NS - 1 < S) stage((s + NS - 1) % NS);
+    const char* A = smem + (s % NS) * STAGE;
+    const char* B = A + BM * KB;
     u32x4 af[KK][TM], bf[KK][TN];
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
       const int ch = kk * 4 + gq;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
-        af[kk][i] = *reinterpret_cast<const u32x4*>(A + (WD ? swz_aw(wm * 64 + 16 * i + r16, ch)
-                                                             : swz_a(wm * 64 + 16 * i + r16, ch)));
+        af[kk][i] = *reinterpret_cast<const u32x4*>(A + swz_a(wm * 64 + 16 * i + r16, ch));
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        bf[kk][j] = *reinterpret_cast<const u32x4*>(B + (WD ? swz_bw(wn * WNC + wrow(j, r16), ch)
-                                                             : swz_b<GS>(wn * WNC + wrow(j, r16), ch)));
+        bf[kk][j] = *reinterpret_cast<const u32x4*>(B + swz_b<GS>(wn * WNC + wrow(j, r16), ch));
     }
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
@@ -300,9 +263,9 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p, int grp
     if constexpr (RELU)
 #pragma unroll
       for (int i = 0; i < TM; ++i) epi_relu(acc[i]);
-    // the old values were loaded before stage(s + NSW - 1): only that stage may stay in flight
+    // the old values were loaded before stage(s + NS - 1): only that stage may stay in flight
     if (ACC) {
-      if (s + NSW - 1 < S) wait_vm<NL>(); else wait_vm<0>();
+      if (s + NS - 1 < S) wait_vm<NL>(); else wait_vm<0>();
     }
     if (STATS) {
       const int srow = (m0 >> 6) + wm;  // 64-row statistics tile
@@ -366,46 +329,25 @@ int cu_count5() {
 }
 
 int g_v5 = 1;  // VU_TUNE_V5: 0 off, 1 on, k >= 2 on with the grid capped at k (tests)
-int g_v5_grp = 0;  // VU_TUNE_V5_GRP
 
 template <int BN, bool STATS, bool ACC>
 int launch5(const VuGemmFwd& p, hipStream_t st) {
   const int64_t M = (int64_t)p.a.N * p.a.H * p.a.W;
-  const int64_t mtiles = M / BM, ntiles = p.ncol / BN;
-  const int64_t T = mtiles * ntiles;
+  const int64_t T = (M / BM) * (p.ncol / BN);
   int64_t grid = T < cu_count5() ? T : cu_count5();
   if (g_v5 >= 2 && grid > g_v5) grid = g_v5;
-  const int grp = g_v5_grp && ntiles >= 8 && ntiles % 8 == 0 && mtiles % 4 == 0 && T % 32 == 0 ? 1 : 0;
   if (p.relu)
-    hipLaunchKernelGGL((gemm_fwd_v5_kernel<BN, STATS, ACC, true>), dim3((unsigned)grid), dim3(NT), 0, st, p, grp);
+    hipLaunchKernelGGL((gemm_fwd_v5_kernel<BN, STATS, ACC, true>), dim3((unsigned)grid), dim3(NT), 0, st, p);
   else
-    hipLaunchKernelGGL((gemm_fwd_v5_kernel<BN, STATS, ACC>), dim3((unsigned)grid), dim3(NT), 0, st, p, grp);
+    hipLaunchKernelGGL((gemm_fwd_v5_kernel<BN, STATS, ACC>), dim3((unsigned)grid), dim3(NT), 0, st, p);
   return (int)hipGetLastError();
 }
 
 template <int BN>
 int launch_bn(const VuGemmFwd& p, hipStream_t st) {
   const bool stats = p.stat_sum != nullptr, acc = p.accumulate != 0;
-  if constexpr (BN == 256) {
-    if (acc) return (int)hipErrorInvalidValue;
-    return stats ? launch5<BN, true, false>(p, st) : launch5<BN, false, false>(p, st);
-  } else {
-    if (stats) return acc ? launch5<BN, true, true>(p, st) : launch5<BN, true, false>(p, st);
-    return acc ? launch5<BN, false, true>(p, st) : launch5<BN, false, false>(p, st);
-  }
-}
-
-int g_v5_wide = 0;  // VU_TUNE_V5_WIDE
-
-// the 256 x 256 tiles: a whole round of tiles (one per CU), no accumulate,
-// ConvTranspose outputs in 32-channel runs, at least two 32-wide K steps
-bool wide_ok(const VuGemmFwd& p) {
-  if (!g_v5_wide || p.accumulate || p.ncol % 256 != 0) return false;
-  if (p.out_mode == 1 && p.cout % 32 != 0) return false;
-  const int64_t M = (int64_t)p.a.N * p.a.H * p.a.W;
-  const int K = p.a.R * p.a.S * p.a.C;
-  if (K < 64) return false;
-  return (M / BM) * (p.ncol / 256) >= cu_count5();
+  if (stats) return acc ? launch5<BN, true, true>(p, st) : launch5<BN, true, false>(p, st);
+  return acc ? launch5<BN, false, true>(p, st) : launch5<BN, false, false>(p, st);
 }
 
 }  // namespace
@@ -431,21 +373,12 @@ int gemm_fwd_v5_bm(const VuGemmFwd& p, int dtype) {
 
 int gemm_fwd_v5_launch(const VuGemmFwd& p, hipStream_t st) {
   if (p.ncol == 64) return launch_bn<64>(p, st);
-  if (wide_ok(p)) return launch_bn<256>(p, st);
   return launch_bn<128>(p, st);
 }
 
 int gemm_fwd_v5_tune(int key, int value) {
   if (key == VU_TUNE_V5) {
     g_v5 = value < 0 ? 0 : value;
-    return 0;
-  }
-  if (key == VU_TUNE_V5_WIDE) {
-    g_v5_wide = value ? 1 : 0;
-    return 0;
-  }
-  if (key == VU_TUNE_V5_GRP) {
-    g_v5_grp = value ? 1 : 0;
     return 0;
   }
   return -1;
