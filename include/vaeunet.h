@@ -126,9 +126,9 @@ typedef struct VuGemmWgrad {
 int vu_gemm_fwd(const VuGemmFwd* args, int dtype, void* stream);
 int64_t vu_gemm_fwd_row_tile(const VuGemmFwd* args, int dtype);  /* BM used */
 /* Pixels per BatchNorm-backward partial row tile when the kernel the
- * dispatcher picks for this problem can emit bnb_part (bf16, 3x3 stride-1
- * kernels: the resident-weight 64 -> 64 kernel and the ping-pong kernel incl.
- * its split-K finish), else 0 (the caller then runs vu_bn_bwd_reduce). */
+ * dispatcher picks for this problem can emit bnb_part (bf16, 3x3 stride-1:
+ * the ping-pong kernel incl. its split-K finish, without zbias), else 0 (the
+ * caller then runs vu_bn_bwd_reduce). */
 int64_t vu_gemm_fwd_bnb_tile(const VuGemmFwd* args, int dtype);
 /* bytes of args->workspace the dispatcher needs for this problem (0 = none):
  * the split-K slabs of the 3x3 kernel when its grid is under one block per CU */
@@ -147,7 +147,11 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
                    int cvalid, int64_t s_i, int64_t s_tap, int64_t s_c,
                    float* out, int accumulate, void* stream);
 
-/* Dispatcher tuning (tests / experiments):
+/* Dispatcher tuning (tests / experiments).  csrc/tuning.hip holds the one
+ * table of keys, defaults and validation; a value outside what a key accepts,
+ * a retired key and an unknown key return hipErrorInvalidValue.  Unless a
+ * range is stated every int is accepted: on/off keys store value != 0, the
+ * "k >= 2" keys store negative values as 0.
  *   VU_TUNE_V4_MIN_BLOCKS: smallest grid for which the ping-pong 3x3 kernel
  *     (gemm_fwd4.hip) is used without split-K (default 256 = one block per
  *     CU; 0 forces it);
@@ -179,7 +183,7 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
 #define VU_TUNE_V5 10
 #define VU_TUNE_V6 11
 /*   VU_TUNE_GEN: highest kernel generation the GEMM dispatchers may pick
- *     (1 = generic only ... 4 = all, the default);
+ *     (1 = generic only ... 4 = all, the default; other values refused);
  *   VU_TUNE_SLAB4: 0 = scalar split-K slab reduce (default 1 = vectorised);
  *   VU_TUNE_BN_NT_MB: streamed-tensor size (MB) from which the BatchNorm
  *     passes use non-temporal loads (default 32; -1 = never).
@@ -190,12 +194,14 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
 /*   VU_TUNE_V7: small-grid 3x3 kernel (gemm_fwd7.hip): 0 = off (v4 split-K /
  *     v2 small-grid tiles), 1 = default (grids under one 256x256 tile per CU,
  *     except 32-pixel-wide ones with >= 512 input channels, which stay on the
- *     ping-pong split-K), 2 = every small grid. */
+ *     ping-pong split-K), 2 = every small grid; other values refused. */
 #define VU_TUNE_V7 16
-/*   VU_TUNE_V7_NBW: weight-ring slots (tap rows) of the small-grid kernel (3 default, 4) */
+/*   VU_TUNE_V7_NBW: weight-ring slots (tap rows) of the small-grid kernel (3 default, 4;
+ *     other values refused) */
 #define VU_TUNE_V7_NBW 17
 /*   VU_TUNE_V7_XM: experiment mode of the small-grid kernel (A/B timing runs
- *     only, results are wrong): 0 off, 2 no DMA inside the loop, 4 no loop */
+ *     only, results are wrong): 0 off, 2 no DMA inside the loop, 4 no loop,
+ *     5 per-phase cycle counters (vu_sg_debug_read) */
 #define VU_TUNE_V7_XM 18
 /*   VU_TUNE_W3_SMALL: 1 (default) lets the halo weight-gradient kernel take
  *     16-pixel-wide images and use 64-channel tiles on small grids; 0 = the
@@ -212,8 +218,9 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
  *     vectors of loads in flight per lane), 0 = one row per iteration; any
  *     other value is refused */
 #define VU_TUNE_ATTN 22
-/*   VU_TUNE_FP8_C64: 1 (default) 64 -> 64 fp8 convs on the resident-weight
- *     tile-stream kernel (statistics row tile 64), 0 = the step-loop kernel */
+/*   VU_TUNE_FP8_C64: 64 -> 64 (and 128 -> 64) fp8 convs on the resident-weight
+ *     tile-stream kernel (statistics row tile 64): 2 (default) with staged
+ *     stores, 1 with direct stores, 0 = off (the step-loop kernel) */
 #define VU_TUNE_FP8_C64 23
 /*   VU_TUNE_FP8_SPLIT: 1 (default) split-K for fp8 grids under one block per
  *     CU (slabs in VuConvFp8.workspace + the split-K finish), 0 off */
@@ -232,12 +239,14 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
 /*   VU_TUNE_V6_XM: experiment modes of the resident-weight 64 -> 64 kernel
  *     (0 default; 1 = s_setprio around each tap's MFMAs; 2-4 = timing
  *     decompositions with wrong results: no in-loop halo DMA, no epilogue
- *     statistics / stores, fragments read once per group). */
+ *     statistics / stores, fragments read once per group; 5 = non-temporal
+ *     output stores, results exact).  Values outside 0..5 are refused. */
 #define VU_TUNE_V6_XM 29
 /*   VU_TUNE_PP_PERSIST: 1 = the ping-pong kernel's 128/256-column tiles as a
  *     persistent walk (one block per CU; the next tile's first halo and
- *     weights stream in during the current tile's epilogue), 0 (default) =
- *     one tile per block. */
+ *     weights stream in during the current tile's epilogue) for grids over
+ *     one block per CU, k >= 2 = always, the grid capped at k blocks (tests),
+ *     0 (default) = one tile per block. */
 #define VU_TUNE_PP_PERSIST 30
 /*   VU_TUNE_BN_ONEPASS: 1 = vu_bn_bwd_fused runs bf16 tensors of at most
  *     8192 pixels as ONE launch (a block per 8 channels reduces and

@@ -12,19 +12,11 @@
 // a 256-thread block owns a 256-pixel tile and emits that tile's BatchNorm(1)
 // partial (sum, centered M2).  Weight-gradient sums use per-block partial
 // slabs reduced in a fixed order (deterministic, no float atomics).
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
 
 constexpr int TILE = 256;  // pixels per block
-
-inline unsigned ew_grid(int64_t work) {
-  int64_t g = (work + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
 
 // Sum over aligned groups of lpp lanes (lpp a power of two, uniform): DPP
 // lane permutations within 16-lane rows (xor 1, xor 2, half-row mirror,
@@ -134,7 +126,6 @@ __global__ void psi_fwd_kernel(const T* ug, const T* ux, int64_t P, int F, const
 // clamped to the last valid row and their results dropped.  Same pixel -> lane
 // assignment and summation order as the one-row kernels (equal up to the
 // compiler's fma contraction of the per-lane sums).
-int g_attn = 1;
 
 template <typename T, int U>
 __global__ __launch_bounds__(256) void psi_fwd_u_kernel(const T* ug, const T* ux, int64_t P, int F, const float* sg,
@@ -735,18 +726,7 @@ __global__ __launch_bounds__(256) void pw_bwd_kernel(const T* x, int64_t xs, con
   }
 }
 
-inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
 }  // namespace
-
-int attn_tune(int key, int value) {
-  if (key == VU_TUNE_ATTN) {
-    if (value != 0 && value != 1) return (int)hipErrorInvalidValue;
-    g_attn = value;
-    return 0;
-  }
-  return -1;
-}
 
 #define DISPATCH_T(dtype, ...) \
   if ((dtype) == VU_BF16) { using T = bf16_t; __VA_ARGS__; } else { using T = float; __VA_ARGS__; }
@@ -761,7 +741,7 @@ extern "C" int vu_attn_psi_fwd(const void* ug, const void* ux, int64_t P, int F,
   if (nblk == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, {
-    if (g_attn)
+    if (tune(VU_TUNE_ATTN))
       hipLaunchKernelGGL((psi_fwd_u_kernel<T, 4>), dim3(nblk), dim3(256), 0, st, (const T*)ug, (const T*)ux, P, F, sg,
                          tg, sx, tx, wpsi, bpsi, q, psum, pm2);
     else
@@ -778,7 +758,7 @@ extern "C" int vu_attn_gate_fwd(const float* q, const float* st_, const void* x,
   if (P == 0) return 0;
   const int V = C / 8;
   DISPATCH_T(dtype, {
-    if (g_attn && pow2(V))
+    if (tune(VU_TUNE_ATTN) && pow2(V))
       hipLaunchKernelGGL((gate_fwd_u_kernel<T, 4>), dim3(ew_grid(P * V / 4)), dim3(256), 0, st, q, st_, (const T*)x,
                          xs, P, __builtin_ctz(V), pmap, (T*)out, os);
     else
@@ -794,7 +774,7 @@ extern "C" int vu_attn_gate_bwd(const void* dout, int64_t dos, const void* x, in
   hipStream_t st = (hipStream_t)stream;
   if (P == 0) return 0;
   DISPATCH_T(dtype, {
-    if (g_attn && C <= 512)
+    if (tune(VU_TUNE_ATTN) && C <= 512)
       hipLaunchKernelGGL((gate_bwd_u_kernel<T, 2>), dim3(ew_grid(P * 8)), dim3(256), 0, st, (const T*)dout, dos,
                          (const T*)x, xs, pmap, P, C, (T*)dx, dxs, dqpre);
     else
@@ -810,7 +790,7 @@ extern "C" int64_t vu_attn_psi_bwd_blocks(int64_t P) {
 }
 
 extern "C" int vu_attn_psi_bwd_bnb_ok(int F) {
-  return F % 8 == 0 && pow2(F / 8) && F / 8 <= 64 && F <= 2048 && g_attn ? 1 : 0;
+  return F % 8 == 0 && pow2(F / 8) && F / 8 <= 64 && F <= 2048 && tune(VU_TUNE_ATTN) ? 1 : 0;
 }
 
 extern "C" int vu_attn_psi_bwd_bnb(const void* ug, const void* ux, int64_t P, int F, const float* sg, const float* tg,
@@ -818,7 +798,7 @@ extern "C" int vu_attn_psi_bwd_bnb(const void* ug, const void* ux, int64_t P, in
                                    float* dwpsi, float* dbpsi, int accumulate, float* workspace,
                                    const float* mean_g, const float* invstd_g, const float* mean_x,
                                    const float* invstd_x, float* bnb_g, float* bnb_x, int dtype, void* stream) {
-  if (F % 8 != 0 || !pow2(F / 8) || F / 8 > 64 || F > 2048 || !g_attn || !mean_g || !invstd_g || !mean_x ||
+  if (F % 8 != 0 || !pow2(F / 8) || F / 8 > 64 || F > 2048 || !tune(VU_TUNE_ATTN) || !mean_g || !invstd_g || !mean_x ||
       !invstd_x || !bnb_g || !bnb_x)
     return (int)hipErrorInvalidValue;
   const int nblk = (int)vu_attn_psi_bwd_blocks(P);
@@ -848,7 +828,7 @@ extern "C" int vu_attn_psi_bwd(const void* ug, const void* ux, int64_t P, int F,
   if (nblk > MAXB) nblk = MAXB;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, {
-    if (g_attn)
+    if (tune(VU_TUNE_ATTN))
       hipLaunchKernelGGL((psi_bwd_u_kernel<T, 4>), dim3(nblk), dim3(256), 0, st, (const T*)ug, (const T*)ux, P, F, sg,
                          tg, sx, tx, wpsi, dq, (T*)ds, workspace);
     else

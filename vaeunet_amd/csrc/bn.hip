@@ -19,8 +19,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
 
@@ -960,15 +959,6 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_apply_kernel(BnBwdFusedArgs 
   }
 }
 
-inline unsigned ew_grid(int64_t work) {
-  int64_t g = (work + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
 // vectorised fixed-channel path: C = 8 * 2^k <= 2048, strides multiples of 8
 inline bool chanmap_ok(int C, int64_t s0, int64_t s1, int64_t s2 = 0) {
   return C % 8 == 0 && pow2(C / 8) && C / 8 <= 256 && s0 % 8 == 0 && s1 % 8 == 0 && s2 % 8 == 0;
@@ -985,17 +975,16 @@ inline unsigned chan_grid16(int64_t P, int C, int maxblk) {
 }
 
 // Launch grid of the streaming kernels: ~16 pixel rows per thread on large
-// tensors, but on small ones at least g_bn_minblk blocks (down to one UNR-deep
+// tensors, but on small ones at least VU_TUNE_BN_MINBLK blocks (down to one UNR-deep
 // load round per thread): a 64-block grid whose threads each wait out four
 // dependent load rounds was latency-bound (9 us for the 4 MB of a ResNet34
-// layer3 BN backward).  VU_TUNE_BN_MINBLK, 0 = the 16-row grid only.
-int g_bn_minblk = 256;
-int g_bn_onepass = 0;  // VU_TUNE_BN_ONEPASS (vu_bn_bwd_fused below; measured slower, off)
+// layer3 BN backward).  0 = the 16-row grid only.
 inline unsigned chan_grid(int64_t P, int C, int maxblk) {
   int R = 256 / (C / 8);
   int64_t g = (P + (int64_t)R * 16 - 1) / ((int64_t)R * 16);
   const int64_t g1 = (P + (int64_t)R * UNR - 1) / ((int64_t)R * UNR);
-  const int64_t lo = g1 < g_bn_minblk ? g1 : g_bn_minblk;
+  const int64_t minblk = tune(VU_TUNE_BN_MINBLK);
+  const int64_t lo = g1 < minblk ? g1 : minblk;
   if (g < lo) g = lo;
   if (g > maxblk) g = maxblk;
   if (g < 1) g = 1;
@@ -1008,9 +997,8 @@ inline unsigned chan_grid(int64_t P, int C, int maxblk) {
 // (profiles/r2_ab_bn_nt.log): UNet 483 -> 491 img/s for any threshold of
 // 0-128 MB; VAE 708 at -1 (never), 701-703 at 0 (always), 708 at 32 MB.
 // Threshold in MB per streamed tensor (VU_TUNE_BN_NT_MB, for A/B runs; -1 = never).
-int g_bn_nt_mb = 32;
 inline bool bn_nt(int64_t P, int C, int esize) {
-  const int64_t mb = g_bn_nt_mb;
+  const int64_t mb = tune(VU_TUNE_BN_NT_MB);
   return mb >= 0 && P * C * esize >= mb * 1000000;
 }
 
@@ -1045,22 +1033,6 @@ int launch_partial(const RedArgs& r, hipStream_t st, int& nblk, int maxblk = RED
 }
 
 }  // namespace
-
-int bn_tune(int key, int value) {
-  if (key == VU_TUNE_BN_NT_MB) {
-    g_bn_nt_mb = value;
-    return 0;
-  }
-  if (key == VU_TUNE_BN_ONEPASS) {
-    g_bn_onepass = value ? 1 : 0;
-    return 0;
-  }
-  if (key == VU_TUNE_BN_MINBLK) {
-    g_bn_minblk = value < 0 ? 0 : value;
-    return 0;
-  }
-  return -1;
-}
 
 extern "C" int64_t vu_reduce_workspace_bytes(int64_t P, int C) {
   (void)P;
@@ -1496,7 +1468,7 @@ extern "C" int vu_bn_bwd_fused(const void* dy, int64_t dys, const void* x, int64
                                int accumulate, void* dx, int64_t dxs, float* workspace, int dtype, void* stream) {
   if (!vu_bn_bwd_fused_supported(P, C, dys, xs, dxs)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  if (g_bn_onepass && dtype == VU_BF16 && P <= ONEPASS_MAXP && dys % 8 == 0 && xs % 8 == 0 && P * (dys > xs ? (dys > dxs ? dys : dxs) : (xs > dxs ? xs : dxs)) < ((int64_t)1 << 31)) {
+  if (tune(VU_TUNE_BN_ONEPASS) && dtype == VU_BF16 && P <= ONEPASS_MAXP && dys % 8 == 0 && xs % 8 == 0 && P * (dys > xs ? (dys > dxs ? dys : dxs) : (xs > dxs ? xs : dxs)) < ((int64_t)1 << 31)) {
     BnBwdFusedArgs a{dy, dys, x, xs, P, C, scale, shift, mean, invstd, gamma, relu, train, nullptr, 0,
                      dgamma, dbeta, accumulate, dx, dxs, 1};
     hipLaunchKernelGGL(bn_bwd_onepass_kernel<bf16_t>, dim3((unsigned)(C / 8)), dim3(ONEPASS_T), 0, st, a);

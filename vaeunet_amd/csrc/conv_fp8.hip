@@ -29,14 +29,11 @@
 //   * epilogue (registers, the next tile's data is in flight in LDS):
 //     acc * x_scale * w_scale[co] (+ bias), bf16 rounding, per-wave (sum,
 //     centered M2) over its 128 pixels, 16-byte NHWC stores.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 #include <cstring>
 
 static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page8[16];
-
-int splitk_finish_launch(const VuGemmFwd& p, hipStream_t st);  // gemm_fwd4.hip
 
 namespace {
 
@@ -219,19 +216,6 @@ VU_DEV i32x8 frag32(const char* base, int row, int h) {
   const u32x4 b = *reinterpret_cast<const u32x4*>(rp + pswz(row, 2 * h + 1));
   return i32x8{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
 }
-
-int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
-int g_grid = 0;  // VU_TUNE_FP8_GRID: grid cap (tests); 0 = CU count
-int g_xm = 0;    // VU_TUNE_FP8_XM: experiment mode (A/B timing only)
 
 // XM: experiment modes (A/B timing only, results wrong): 1 = no MFMAs, 2 = no DMA in the loop
 template <int BN, int XM = 0>
@@ -1139,12 +1123,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_c64_kernel(VuConvFp8 p) {
   }
 }
 
-int g_c64 = 2;  // VU_TUNE_FP8_C64: 2 (default) resident-weight kernel, staged stores; 1 direct stores; 0 off
-
+// VU_TUNE_FP8_C64: 2 (default) resident-weight kernel, staged stores; 1 direct stores; 0 off
 // 64-channel chunks the resident-weight kernel walks per tile (1 or 2), 0 = not served
 int c64_nch(const VuConvFp8& p) {
   const VuGather& g = p.a;
-  if (!g_c64 || p.ncol != 64 || (g.C != 64 && g.C != 128)) return 0;
+  if (!tune(VU_TUNE_FP8_C64) || p.ncol != 64 || (g.C != 64 && g.C != 128)) return 0;
   for (int t = 0; t < g.nsrc; ++t)
     if (g.cend[t] % 64) return 0;
   if (g.H % C64_TH != 0 || g.W % C64_TW != 0) return 0;
@@ -1155,7 +1138,7 @@ int c64_nch(const VuConvFp8& p) {
 
 bool c64_ok(const VuConvFp8& p) {
   const VuGather& g = p.a;
-  if (!g_c64 || g.nsrc != 1 || g.C != 64 || g.cend[0] != 64 || p.ncol != 64) return false;
+  if (!tune(VU_TUNE_FP8_C64) || g.nsrc != 1 || g.C != 64 || g.cend[0] != 64 || p.ncol != 64) return false;
   if (g.H % C64_TH != 0 || g.W % C64_TW != 0) return false;
   const int64_t T = (int64_t)g.N * (g.H / C64_TH) * (g.W / C64_TW);
   return T >= 2 * (int64_t)cu_count();  // a tile stream per block
@@ -1176,9 +1159,7 @@ int pick_bn(const VuConvFp8& p) {
 
 bool served(const VuConvFp8& p) {
   const VuGather& g = p.a;
-  if (g.R != 3 || g.S != 3 || g.sy != 1 || g.sx != 1 || g.dy != 1 || g.dx != 1 || g.oy != -1 || g.ox != -1 ||
-      g.Hs != g.H || g.Ws != g.W || g.nsrc < 1 || g.nsrc > 3)
-    return false;
+  if (!same3x3(g) || g.nsrc < 1 || g.nsrc > 3) return false;
   if (g.C % 64 != 0 || g.C < 64) return false;
   for (int t = 0; t < g.nsrc; ++t)
     if (g.cend[t] % 64 != 0 || g.stride[t] % 16 != 0) return false;
@@ -1187,10 +1168,6 @@ bool served(const VuConvFp8& p) {
   if ((int64_t)g.N * g.H * g.W >= (int64_t)1 << 31) return false;
   return pick_bn(p) != 0;
 }
-
-int g_pp = 1;  // VU_TUNE_FP8_PP: 1 (default) one tile per block on the ping-pong step loop, 0 persistent (A/B)
-
-int g_split = 1;  // VU_TUNE_FP8_SPLIT: 1 (default) split-K for grids under one block per CU, 0 off
 
 template <int BN>
 int64_t bn_tiles(const VuConvFp8& p) {
@@ -1201,9 +1178,11 @@ int64_t bn_tiles(const VuConvFp8& p) {
 // split factor of the step-loop kernel: tiles < CUs -> ceil(CUs / tiles)
 // chunk ranges of >= 8 chunks each (at batch 2 / 1024^2: down4.2, 1024
 // channels, 129 -> 117 us; down4.1 with 512 would be 73 -> 87 us -- the slab
-// round trip costs more than the idle half of the chip there)
+// round trip costs more than the idle half of the chip there).
+// VU_TUNE_FP8_SPLIT 0 turns it off; VU_TUNE_FP8_PP 0 and a VU_TUNE_FP8_GRID
+// cap (tests) select the persistent kernel, which has no split.
 int fp8_ksplit(const VuConvFp8& p) {
-  if (!g_split || !g_pp || g_grid != 0 || c64_nch(p)) return 1;
+  if (!tune(VU_TUNE_FP8_SPLIT) || !tune(VU_TUNE_FP8_PP) || tune(VU_TUNE_FP8_GRID) != 0 || c64_nch(p)) return 1;
   const int bn = pick_bn(p);
   const int64_t tiles = bn == 256 ? bn_tiles<256>(p) : bn == 128 ? bn_tiles<128>(p) : bn_tiles<64>(p);
   const int64_t M = (int64_t)p.a.N * p.a.H * p.a.W;
@@ -1238,25 +1217,25 @@ int launch(const VuConvFp8& p, hipStream_t st) {
     q.accumulate = 0;
     return splitk_finish_launch(q, st);
   }
-  if (g_pp && g_grid == 0) {
+  if (tune(VU_TUNE_FP8_PP) && tune(VU_TUNE_FP8_GRID) == 0) {
     if (p.stat_min) {
-      if (g_xm != 0) return (int)hipErrorInvalidValue;
+      if (tune(VU_TUNE_FP8_XM) != 0) return (int)hipErrorInvalidValue;
       hipLaunchKernelGGL((conv3x3_fp8_pp_kernel<BN, 0, false, true>), dim3((unsigned)tiles), dim3(512), 0, st, p);
       return (int)hipGetLastError();
     }
-    if (g_xm == 1)
+    if (tune(VU_TUNE_FP8_XM) == 1)
       hipLaunchKernelGGL((conv3x3_fp8_pp_kernel<BN, 1>), dim3((unsigned)tiles), dim3(512), 0, st, p);
-    else if (g_xm == 2)
+    else if (tune(VU_TUNE_FP8_XM) == 2)
       hipLaunchKernelGGL((conv3x3_fp8_pp_kernel<BN, 2>), dim3((unsigned)tiles), dim3(512), 0, st, p);
     else
       hipLaunchKernelGGL((conv3x3_fp8_pp_kernel<BN>), dim3((unsigned)tiles), dim3(512), 0, st, p);
     return (int)hipGetLastError();
   }
-  const int64_t cap = g_grid > 0 ? g_grid : cu_count();
+  const int64_t cap = tune(VU_TUNE_FP8_GRID) > 0 ? tune(VU_TUNE_FP8_GRID) : cu_count();
   const int64_t nblk = tiles < cap ? tiles : cap;
-  if (g_xm == 1)
+  if (tune(VU_TUNE_FP8_XM) == 1)
     hipLaunchKernelGGL((conv3x3_fp8_kernel<BN, 1>), dim3((unsigned)nblk), dim3(512), 0, st, p);
-  else if (g_xm == 2)
+  else if (tune(VU_TUNE_FP8_XM) == 2)
     hipLaunchKernelGGL((conv3x3_fp8_kernel<BN, 2>), dim3((unsigned)nblk), dim3(512), 0, st, p);
   else
     hipLaunchKernelGGL((conv3x3_fp8_kernel<BN>), dim3((unsigned)nblk), dim3(512), 0, st, p);
@@ -1486,30 +1465,6 @@ __global__ __launch_bounds__(256) void relu_amax_kernel(const float* pmin, const
 
 }  // namespace
 
-int conv_fp8_tune(int key, int value) {
-  if (key == VU_TUNE_FP8_SPLIT) {
-    g_split = value != 0;
-    return 0;
-  }
-  if (key == VU_TUNE_FP8_GRID) {
-    g_grid = value;
-    return 0;
-  }
-  if (key == VU_TUNE_FP8_XM) {
-    g_xm = value;
-    return 0;
-  }
-  if (key == VU_TUNE_FP8_PP) {
-    g_pp = value != 0;
-    return 0;
-  }
-  if (key == VU_TUNE_FP8_C64) {
-    g_c64 = value < 0 ? 0 : value;
-    return 0;
-  }
-  return -1;
-}
-
 extern "C" int64_t vu_conv3x3_fp8_row_tile(const VuConvFp8* args) {
   if (!served(*args)) return 0;
   return c64_nch(*args) ? 64 : 128;
@@ -1526,10 +1481,10 @@ extern "C" int64_t vu_conv3x3_fp8_workspace_bytes(const VuConvFp8* args) {
 // resident-weight kernels; not the persistent (VU_TUNE_FP8_PP 0 / capped grid)
 // or split-K paths, nor experiment modes
 extern "C" int vu_conv3x3_fp8_minmax_ok(const VuConvFp8* args) {
-  if (!served(*args) || g_xm != 0) return 0;
+  if (!served(*args) || tune(VU_TUNE_FP8_XM) != 0) return 0;
   if (c64_nch(*args) == 2) return 1;
   if (c64_ok(*args)) return 1;
-  return (g_pp && g_grid == 0 && fp8_ksplit(*args) <= 1) ? 1 : 0;
+  return (tune(VU_TUNE_FP8_PP) && tune(VU_TUNE_FP8_GRID) == 0 && fp8_ksplit(*args) <= 1) ? 1 : 0;
 }
 
 extern "C" int vu_conv3x3_fp8(const VuConvFp8* args, void* stream) {
@@ -1559,18 +1514,18 @@ extern "C" int vu_conv3x3_fp8(const VuConvFp8* args, void* stream) {
     const VuGather& g = args->a;
     const int64_t T = (int64_t)g.N * (g.H / C64_TH) * (g.W / C64_TW);
     const int64_t grid = T < cu_count() ? T : cu_count();
-    if (g_xm >= 1 && g_xm <= 4 && args->stat_sum) {
-      if (g_xm == 4)
+    if (tune(VU_TUNE_FP8_XM) >= 1 && tune(VU_TUNE_FP8_XM) <= 4 && args->stat_sum) {
+      if (tune(VU_TUNE_FP8_XM) == 4)
         hipLaunchKernelGGL((conv3x3_fp8_c64_kernel<true, true, 4>), dim3((unsigned)grid), dim3(512), 0, st, *args);
-      else if (g_xm == 1)
+      else if (tune(VU_TUNE_FP8_XM) == 1)
         hipLaunchKernelGGL((conv3x3_fp8_c64_kernel<true, true, 1>), dim3((unsigned)grid), dim3(512), 0, st, *args);
-      else if (g_xm == 2)
+      else if (tune(VU_TUNE_FP8_XM) == 2)
         hipLaunchKernelGGL((conv3x3_fp8_c64_kernel<true, true, 2>), dim3((unsigned)grid), dim3(512), 0, st, *args);
       else
         hipLaunchKernelGGL((conv3x3_fp8_c64_kernel<true, true, 3>), dim3((unsigned)grid), dim3(512), 0, st, *args);
       return (int)hipGetLastError();
     }
-    if (args->stat_min) {  // (the staging-strip variant, g_c64 >= 2, has no min / max epilogue)
+    if (args->stat_min) {  // (the staging-strip variant, tune(VU_TUNE_FP8_C64) >= 2, has no min / max epilogue)
       if (args->stat_sum)
         hipLaunchKernelGGL((conv3x3_fp8_c64_kernel<true, false, 0, 1, true>), dim3((unsigned)grid), dim3(512), 0, st,
                            *args);
@@ -1579,7 +1534,7 @@ extern "C" int vu_conv3x3_fp8(const VuConvFp8* args, void* stream) {
                            *args);
       return (int)hipGetLastError();
     }
-    if (g_c64 >= 2) {
+    if (tune(VU_TUNE_FP8_C64) >= 2) {
       if (args->stat_sum)
         hipLaunchKernelGGL((conv3x3_fp8_c64_kernel<true, true>), dim3((unsigned)grid), dim3(512), 0, st, *args);
       else

@@ -16,8 +16,7 @@
 //     (as gemm_fwd5.hip) so a lane holds 16 consecutive output channels of one
 //     pixel: two 16-byte NHWC stores per fragment, BatchNorm partials per
 //     64-pixel wave tile by DPP row sums.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
 
@@ -174,16 +173,6 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_image_kernel(VuGemmFwd p) {
   }
 }
 
-int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace
 
 // Row tile (64) when this kernel serves the problem, else 0: bf16 3x3
@@ -192,9 +181,7 @@ int cu_count() {
 int conv_image_bm(const VuGemmFwd& p, int dtype) {
   const VuGather& g = p.a;
   if (dtype != VU_BF16 || p.out_mode != 0 || p.accumulate) return 0;
-  if (g.R != 3 || g.S != 3 || g.sy != 1 || g.sx != 1 || g.dy != 1 || g.dx != 1 || g.oy != -1 ||
-      g.ox != -1 || g.Hs != g.H || g.Ws != g.W || g.nsrc != 1 || g.C != 8)
-    return 0;
+  if (!same3x3(g) || g.nsrc != 1 || g.C != 8) return 0;
   if (g.stride[0] % 8 != 0 || p.ncol % 64 != 0 || p.ldb % 8 != 0 || p.ldb < 72) return 0;
   if (p.out_stride % 8 != 0 || p.out_coff % 8 != 0) return 0;
   const int64_t M = (int64_t)g.N * g.H * g.W;

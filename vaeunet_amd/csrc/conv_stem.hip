@@ -18,8 +18,7 @@
 //     consecutive output channels of one pixel), bias, bf16 rounding,
 //     BatchNorm partials per 64-pixel wave tile (DPP row sums) and
 //     permlane-regrouped stores of 64 contiguous bytes per pixel.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
 
@@ -186,16 +185,6 @@ __global__ __launch_bounds__(NT, 2) void conv_stem_kernel(VuGemmFwd p) {
   }
 }
 
-int cu_count_stem() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace
 
 // Row tile (64) when this kernel serves the problem, else 0: bf16 7x7
@@ -217,7 +206,7 @@ int conv_stem_bm(const VuGemmFwd& p, int dtype) {
 int conv_stem_launch(const VuGemmFwd& p, hipStream_t st) {
   const int64_t tiles = (int64_t)p.a.N * p.a.H * p.a.W / TP;
   int64_t nblk = (tiles + 3) / 4;
-  const int64_t cap = 2 * (int64_t)cu_count_stem();  // persistent: 2 blocks (8 waves) per CU
+  const int64_t cap = 2 * (int64_t)cu_count();  // persistent: 2 blocks (8 waves) per CU
   if (nblk > cap) nblk = cap;
   if (p.relu)
     hipLaunchKernelGGL(conv_stem_kernel<true>, dim3((unsigned)nblk), dim3(NT), 0, st, p);

@@ -21,8 +21,7 @@
 // statistics (sum, centered M2) on the dtype-rounded values and writes
 // 16-byte coalesced rows.
 #include <stdlib.h>
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
 
@@ -362,127 +361,90 @@ int dispatch_fwd(const VuGemmFwd& p, hipStream_t st) {
   return launch_fwd<T, 64, 64>(p, st);
 }
 
-}  // namespace
+// One kernel the dispatcher may pick.  kRoutes lists them in dispatch order:
+// the first route that is admitted and serves a problem runs it, and the
+// row-tile, workspace, BatchNorm-backward-tile and kernel-id queries answer
+// for that same route.
+struct Route {
+  int id;   // vu_gemm_fwd_kernel
+  int gen;  // lowest VU_TUNE_GEN that admits it; above 1: bf16 only
+  // zbias: its epilogue adds VuGemmFwd.zbias, the per-sample border-class bias
+  // (such problems skip every other route)
+  bool zbias;
+  int (*serves)(const VuGemmFwd&, int dtype);  // the row tile, 0 = declines
+  int (*launch)(const VuGemmFwd&, hipStream_t);
+  int64_t (*workspace)(const VuGemmFwd&, int dtype);  // optional: bytes of VuGemmFwd.workspace
+  int (*bnb_tile)(const VuGemmFwd&, int dtype);       // optional: BatchNorm-backward partial tile
+};
 
-// large-tile LDS-DMA variant (gemm_fwd2.hip)
-int gemm_fwd_v2_bm(const VuGemmFwd& p, int dtype);
-int gemm_fwd_v2_launch(const VuGemmFwd& p, hipStream_t st);
-int gemm_fwd_v2_small(const VuGemmFwd& p, int dtype);
-int gemm_fwd_v2_small_launch(const VuGemmFwd& p, hipStream_t st);
-int gemm_fwd_v2_tail(const VuGemmFwd& p, int dtype);
-int gemm_fwd_v2_tail_launch(const VuGemmFwd& p, hipStream_t st);
-int64_t gemm_fwd_v2_small_workspace(const VuGemmFwd& p, int dtype);
-int gemm_fwd_v3_bm(const VuGemmFwd& p, int dtype);
-int gemm_fwd_v3_launch(const VuGemmFwd& p, hipStream_t st);
-int gemm_fwd_v4_bm(const VuGemmFwd& p, int dtype);
-int gemm_fwd_v4_launch(const VuGemmFwd& p, hipStream_t st);
-int64_t gemm_fwd_v4_workspace(const VuGemmFwd& p, int dtype);
-int conv_image_bm(const VuGemmFwd& p, int dtype);      // conv_image.hip (3-channel image conv)
-int conv_stem_bm(const VuGemmFwd& p, int dtype);       // conv_stem.hip (ResNet34 7x7/s2 stem)
-int conv_stem_launch(const VuGemmFwd& p, hipStream_t st);
-int conv_image_launch(const VuGemmFwd& p, hipStream_t st);
-int gemm_stream_bm(const VuGemmFwd& p, int dtype);     // gemm_stream.hip (short-K 1x1 streams)
-int gemm_stream_launch(const VuGemmFwd& p, hipStream_t st);
-int gemm_fwd_v5_bm(const VuGemmFwd& p, int dtype);     // gemm_fwd5.hip (persistent short-K GEMM)
-int gemm_fwd_v5_launch(const VuGemmFwd& p, hipStream_t st);
-int gemm_fwd_v6_bm(const VuGemmFwd& p, int dtype);     // gemm_fwd6.hip (64 -> 64 3x3, resident weights)
-int gemm_fwd_v6_launch(const VuGemmFwd& p, hipStream_t st);
-int gemm_fwd_v6_bnb_tile(const VuGemmFwd& p, int dtype);
-int gemm_fwd_v4_bnb_tile(const VuGemmFwd& p, int dtype);
-int gemm_fwd_v7_bm(const VuGemmFwd& p, int dtype);     // gemm_fwd7.hip (small-grid 3x3, two K groups)
-int gemm_fwd_v7_launch(const VuGemmFwd& p, hipStream_t st);
-int64_t gemm_fwd_v7_workspace(const VuGemmFwd& p, int dtype);
+// (gemm_fwd_v2_small returns its split count: the row tile is 128)
+int v2_small_bm(const VuGemmFwd& p, int dtype) { return gemm_fwd_v2_small(p, dtype) ? 128 : 0; }
 
-// Highest kernel generation the dispatchers may pick (vu_gemm_set_tuning
-// VU_TUNE_GEN; tests and A/B runs only -- no environment lookups in the
-// library): 1 = generic kernels only, 2 = + LDS-DMA tiles / 1x1 streams,
-// 3 = + halo kernels, 4 (default) = + ping-pong / resident-weight kernels.
-int g_tune_gen = 4;
+// the register-staged kernel of this file, one route per storage type
+int generic_bf16_bm(const VuGemmFwd& p, int dtype) { return dtype == VU_BF16 ? pick_bm(p) : 0; }
+int generic_f32_bm(const VuGemmFwd& p, int dtype) { return dtype != VU_BF16 ? pick_bm(p) : 0; }
 
-static bool use_v2(int dtype) { return g_tune_gen >= 2 && dtype == VU_BF16; }
-static bool use_v3(int dtype) { return g_tune_gen >= 3 && use_v2(dtype); }
-static bool use_v4(int dtype) { return g_tune_gen >= 4 && use_v3(dtype); }
+// VU_TUNE_GEN (tests and A/B runs): 1 = generic kernels only, 2 = + LDS-DMA
+// tiles / 1x1 streams, 3 = + halo kernels, 4 (default) = + ping-pong /
+// resident-weight kernels.
+const Route kRoutes[] = {
+    {9, 2, false, conv_image_bm, conv_image_launch},
+    {10, 2, false, conv_stem_bm, conv_stem_launch},
+    {8, 2, false, gemm_stream_bm, gemm_stream_launch},
+    {6, 4, false, gemm_fwd_v6_bm, gemm_fwd_v6_launch},
+    {4, 4, true, gemm_fwd_v4_bm, gemm_fwd_v4_launch, gemm_fwd_v4_workspace, gemm_fwd_v4_bnb_tile},
+    {7, 4, false, gemm_fwd_v7_bm, gemm_fwd_v7_launch, gemm_fwd_v7_workspace},
+    {12, 2, false, v2_small_bm, gemm_fwd_v2_small_launch, gemm_fwd_v2_small_workspace},
+    {3, 3, false, gemm_fwd_v3_bm, gemm_fwd_v3_launch},
+    {5, 2, false, gemm_fwd_v5_bm, gemm_fwd_v5_launch},
+    {2, 2, false, gemm_fwd_v2_bm, gemm_fwd_v2_launch},
+    {13, 2, false, gemm_fwd_v2_tail, gemm_fwd_v2_tail_launch},
+    {1, 1, true, generic_bf16_bm, dispatch_fwd<bf16_t>},
+    {1, 1, true, generic_f32_bm, dispatch_fwd<float>},
+};
 
-// VuGemmFwd.zbias problems run on the ping-pong kernel (incl. its split-K
-// finish) when it serves them, else on the generic kernel: the only two
-// epilogues that add the per-sample border-class bias
-static bool zb_v4(const VuGemmFwd* a, int dtype) { return use_v4(dtype) && gemm_fwd_v4_bm(*a, dtype); }
-static bool zb_ok(const VuGemmFwd* a) {
-  return a->out_mode == 0 && a->a.H >= 2 && a->a.W >= 2 && !a->bnb_part;
+// The route that runs this problem; *bm receives its row tile.  (The generic
+// routes decline nothing, so there always is one.)
+const Route& pick(const VuGemmFwd& p, int dtype, int* bm = nullptr) {
+  const int gen = tune(VU_TUNE_GEN);
+  for (const Route& r : kRoutes) {
+    if (r.gen > 1 && (gen < r.gen || dtype != VU_BF16)) continue;
+    if (p.zbias && !r.zbias) continue;
+    if (const int t = r.serves(p, dtype)) {
+      if (bm) *bm = t;
+      return r;
+    }
+  }
+  abort();
 }
 
+}  // namespace
+
 extern "C" int64_t vu_gemm_fwd_row_tile(const VuGemmFwd* args, int dtype) {
-  if (args->zbias) return zb_v4(args, dtype) ? 128 : pick_bm(*args);
-  if (use_v2(dtype)) {
-    int bm = conv_image_bm(*args, dtype);
-    if (bm) return bm;
-    bm = conv_stem_bm(*args, dtype);
-    if (bm) return bm;
-    bm = gemm_stream_bm(*args, dtype);
-    if (bm) return bm;
-  }
-  if (use_v4(dtype)) {
-    int bm = gemm_fwd_v6_bm(*args, dtype);
-    if (bm) return bm;
-    bm = gemm_fwd_v4_bm(*args, dtype);
-    if (bm) return bm;
-    bm = gemm_fwd_v7_bm(*args, dtype);
-    if (bm) return bm;
-  }
-  if (use_v2(dtype) && gemm_fwd_v2_small(*args, dtype)) return 128;
-  if (use_v3(dtype) && gemm_fwd_v3_bm(*args, dtype)) return 256;
-  if (use_v2(dtype)) {
-    int bm = gemm_fwd_v5_bm(*args, dtype);
-    if (bm) return bm;
-    bm = gemm_fwd_v2_bm(*args, dtype);
-    if (bm) return bm;
-    bm = gemm_fwd_v2_tail(*args, dtype);
-    if (bm) return bm;
-  }
-  return pick_bm(*args);
+  int bm;
+  pick(*args, dtype, &bm);
+  return bm;
 }
 
 extern "C" int64_t vu_gemm_fwd_workspace_bytes(const VuGemmFwd* args, int dtype) {
-  if (args->zbias) return zb_v4(args, dtype) ? gemm_fwd_v4_workspace(*args, dtype) : 0;
-  if (use_v2(dtype) && (conv_image_bm(*args, dtype) || conv_stem_bm(*args, dtype) || gemm_stream_bm(*args, dtype)))
-    return 0;
-  if (use_v4(dtype) && gemm_fwd_v6_bm(*args, dtype)) return 0;
-  if (use_v4(dtype) && gemm_fwd_v4_bm(*args, dtype)) return gemm_fwd_v4_workspace(*args, dtype);
-  if (use_v4(dtype) && gemm_fwd_v7_bm(*args, dtype)) return gemm_fwd_v7_workspace(*args, dtype);
-  if (use_v2(dtype) && gemm_fwd_v2_small(*args, dtype)) return gemm_fwd_v2_small_workspace(*args, dtype);
-  return 0;
+  const Route& r = pick(*args, dtype);
+  return r.workspace ? r.workspace(*args, dtype) : 0;
 }
 
-// The BatchNorm-backward partial tile of the kernel the dispatcher below picks
-// (it must mirror the dispatch order), 0 when that kernel cannot emit them.
+// The BatchNorm-backward partial tile of the route, 0 when its kernel cannot
+// emit them.
 extern "C" int64_t vu_gemm_fwd_bnb_tile(const VuGemmFwd* args, int dtype) {
-  if (args->zbias) return 0;
-  if (use_v2(dtype) && (conv_image_bm(*args, dtype) || conv_stem_bm(*args, dtype) || gemm_stream_bm(*args, dtype)))
-    return 0;
-  if (use_v4(dtype) && gemm_fwd_v6_bm(*args, dtype)) return gemm_fwd_v6_bnb_tile(*args, dtype);
-  if (use_v4(dtype) && gemm_fwd_v4_bm(*args, dtype)) return gemm_fwd_v4_bnb_tile(*args, dtype);
-  return 0;
+  const Route& r = pick(*args, dtype);
+  return r.bnb_tile ? r.bnb_tile(*args, dtype) : 0;
 }
 
-// Which kernel the dispatcher below picks (mirrors its order; tests assert the
-// path they mean to cover): 1 generic, 2 v2 LDS-DMA tiles, 3 v3 halo, 4 v4
-// ping-pong, 5 v5 persistent short-K, 6 v6 resident weights, 7 v7 small-grid,
-// 8 1x1 stream, 9 image conv, 10 7x7 stem, 12 v2 small-grid mode, 13 v2
-// tail (small grids nothing else admits).
+// Which kernel runs this problem (tests assert the path they mean to cover):
+// 1 generic, 2 v2 LDS-DMA tiles, 3 v3 halo, 4 v4 ping-pong, 5 v5 persistent
+// short-K, 6 v6 resident weights, 7 v7 small-grid, 8 1x1 stream, 9 image conv,
+// 10 7x7 stem, 12 v2 small-grid mode, 13 v2 tail (small grids nothing else
+// admits).
 extern "C" int vu_gemm_fwd_kernel(const VuGemmFwd* args, int dtype) {
-  if (args->zbias) return zb_v4(args, dtype) ? 4 : 1;
-  if (use_v2(dtype) && conv_image_bm(*args, dtype)) return 9;
-  if (use_v2(dtype) && conv_stem_bm(*args, dtype)) return 10;
-  if (use_v2(dtype) && gemm_stream_bm(*args, dtype)) return 8;
-  if (use_v4(dtype) && gemm_fwd_v6_bm(*args, dtype)) return 6;
-  if (use_v4(dtype) && gemm_fwd_v4_bm(*args, dtype)) return 4;
-  if (use_v4(dtype) && gemm_fwd_v7_bm(*args, dtype)) return 7;
-  if (use_v2(dtype) && gemm_fwd_v2_small(*args, dtype)) return 12;
-  if (use_v3(dtype) && gemm_fwd_v3_bm(*args, dtype)) return 3;
-  if (use_v2(dtype) && gemm_fwd_v5_bm(*args, dtype)) return 5;
-  if (use_v2(dtype) && gemm_fwd_v2_bm(*args, dtype)) return 2;
-  if (use_v2(dtype) && gemm_fwd_v2_tail(*args, dtype)) return 13;
-  return 1;
+  return pick(*args, dtype).id;
 }
 
 extern "C" int vu_gemm_fwd(const VuGemmFwd* args, int dtype, void* stream) {
@@ -494,24 +456,8 @@ extern "C" int vu_gemm_fwd(const VuGemmFwd* args, int dtype, void* stream) {
   for (int t = 0; t < g.nsrc; ++t)
     if (g.cend[t] % epc != 0 || g.stride[t] % epc != 0) return (int)hipErrorInvalidValue;
   if ((args->ldb % epc) != 0) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  if (args->zbias) {
-    if (!zb_ok(args)) return (int)hipErrorInvalidValue;
-    if (zb_v4(args, dtype)) return gemm_fwd_v4_launch(*args, st);
-    return dtype == VU_BF16 ? dispatch_fwd<bf16_t>(*args, st) : dispatch_fwd<float>(*args, st);
-  }
-  if (use_v2(dtype) && conv_image_bm(*args, dtype)) return conv_image_launch(*args, st);
-  if (use_v2(dtype) && conv_stem_bm(*args, dtype)) return conv_stem_launch(*args, st);
-  if (use_v2(dtype) && gemm_stream_bm(*args, dtype)) return gemm_stream_launch(*args, st);
-  if (use_v4(dtype) && gemm_fwd_v6_bm(*args, dtype)) return gemm_fwd_v6_launch(*args, st);
-  if (use_v4(dtype) && gemm_fwd_v4_bm(*args, dtype)) return gemm_fwd_v4_launch(*args, st);
-  if (use_v4(dtype) && gemm_fwd_v7_bm(*args, dtype)) return gemm_fwd_v7_launch(*args, st);
-  if (use_v2(dtype) && gemm_fwd_v2_small(*args, dtype)) return gemm_fwd_v2_small_launch(*args, st);
-  if (use_v3(dtype) && gemm_fwd_v3_bm(*args, dtype)) return gemm_fwd_v3_launch(*args, st);
-  if (use_v2(dtype) && gemm_fwd_v5_bm(*args, dtype)) return gemm_fwd_v5_launch(*args, st);
-  if (use_v2(dtype) && gemm_fwd_v2_bm(*args, dtype)) return gemm_fwd_v2_launch(*args, st);
-  if (use_v2(dtype) && gemm_fwd_v2_tail(*args, dtype)) return gemm_fwd_v2_tail_launch(*args, st);
-  return dtype == VU_BF16 ? dispatch_fwd<bf16_t>(*args, st) : dispatch_fwd<float>(*args, st);
+  if (args->zbias && (args->out_mode != 0 || g.H < 2 || g.W < 2 || args->bnb_part)) return (int)hipErrorInvalidValue;
+  return pick(*args, dtype).launch(*args, (hipStream_t)stream);
 }
 
 extern "C" void vu_abi_struct_sizes(int64_t* out) {

@@ -20,8 +20,7 @@
 //     fp32), BatchNorm partial statistics on exactly those values, 16-byte
 //     coalesced stores; out_mode 1 scatters the ConvTranspose2d(k=2, s=2)
 //     pixel shuffle, out_mode 2 a stride-2 parity lattice.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 #include <stdlib.h>
 
 static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page[16];  // 16 B of zeros: padding lanes DMA from here
@@ -381,15 +380,14 @@ int gemm_fwd_v2_bm(const VuGemmFwd& p, int dtype) {
 // kernels' 32-pixel rows): 128 x 64 tiles of 4 waves, two blocks per CU,
 // split-K to >= 2 blocks per CU when the tiles alone do not reach it (fp32
 // slabs + the deterministic finish of gemm_fwd4.hip).  Returns the split
-// (>= 1) when served, else 0.
-bool g_small = true;  // VU_TUNE_V2_SMALL
-
+// (>= 1) when served, else 0.  VU_TUNE_V2_SMALL = 0 turns it off.
+//
 // (The stride-2 parity-class input gradients -- out_mode 2 -- measured 0.3 %
 // slower end to end on these tiles than on the generic kernel, VAE same-box
 // A/B profiles/r3_ab_parity_v2small.log; they stay there.  splitk_finish_kernel
 // handles out_mode 2 all the same.)
 int gemm_fwd_v2_small(const VuGemmFwd& p, int dtype) {
-  if (!g_small || dtype != VU_BF16 || p.out_mode != 0) return 0;
+  if (!tune(VU_TUNE_V2_SMALL) || dtype != VU_BF16 || p.out_mode != 0) return 0;
   const VuGather& g = p.a;
   for (int t = 0; t < g.nsrc; ++t)
     if (g.stride[t] % 8 != 0 || g.cend[t] % 64 != 0) return 0;
@@ -409,8 +407,6 @@ int64_t gemm_fwd_v2_small_workspace(const VuGemmFwd& p, int dtype) {
   const int ks = gemm_fwd_v2_small(p, dtype);
   return ks > 1 ? (int64_t)ks * p.a.N * p.a.H * p.a.W * p.ncol * (int64_t)sizeof(float) : 0;
 }
-
-int splitk_finish_launch(const VuGemmFwd& p, hipStream_t st);  // gemm_fwd4.hip
 
 int gemm_fwd_v2_small_launch(const VuGemmFwd& p, hipStream_t st) {
   const int ks = gemm_fwd_v2_small(p, VU_BF16);
@@ -432,18 +428,10 @@ int gemm_fwd_v2_small_launch(const VuGemmFwd& p, hipStream_t st) {
 // few microseconds, and the generic register-staged kernel they fell to took
 // ~11 us each (round-3 config-3 profile).  VU_TUNE_V2_SMALL = 0 turns it off.
 int gemm_fwd_v2_tail(const VuGemmFwd& p, int dtype) {
-  return g_small && v2_shape_ok(p, dtype) ? 128 : 0;
+  return tune(VU_TUNE_V2_SMALL) && v2_shape_ok(p, dtype) ? 128 : 0;
 }
 
 int gemm_fwd_v2_tail_launch(const VuGemmFwd& p, hipStream_t st) { return launch_ns<128, 64, 2, 2>(p, st); }
-
-int gemm_fwd_v2_tune(int key, int value) {
-  if (key == VU_TUNE_V2_SMALL) {
-    g_small = value != 0;
-    return 0;
-  }
-  return -1;
-}
 
 int gemm_fwd_v2_launch(const VuGemmFwd& p, hipStream_t st) {
   if (p.ncol <= 64) return launch_ns<256, 64, 8, 1>(p, st);

@@ -22,8 +22,7 @@
 //     wait is a COUNTED vmcnt followed by a raw s_barrier;
 //   * epilogue identical to v1/v2: fp32 tile in LDS, BatchNorm per-tile
 //     (sum, centered M2) on the bf16-rounded values, 16-byte stores.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page3[16];
 
@@ -304,10 +303,7 @@ int pick_tw(const VuGather& g) {
 // source groups, plain NHWC output, and an image that tiles by 8x32 / 16x16.
 int gemm_fwd_v3_bm(const VuGemmFwd& p, int dtype) {
   const VuGather& g = p.a;
-  if (dtype != VU_BF16 || p.out_mode != 0) return 0;
-  if (g.R != 3 || g.S != 3 || g.sy != 1 || g.sx != 1 || g.dy != 1 || g.dx != 1 || g.oy != -1 ||
-      g.ox != -1 || g.Hs != g.H || g.Ws != g.W)
-    return 0;
+  if (dtype != VU_BF16 || p.out_mode != 0 || !same3x3(g)) return 0;
   if (g.C % 64 != 0) return 0;
   for (int t = 0; t < g.nsrc; ++t)
     if (g.cend[t] % 64 != 0 || g.stride[t] % 8 != 0) return 0;

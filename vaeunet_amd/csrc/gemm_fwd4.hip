@@ -41,8 +41,7 @@
 //     256 CUs): each block walks a contiguous range of 32-channel chunks and
 //     writes its fp32 tile to a slab; splitk_finish_kernel sums the slabs in
 //     a fixed order and applies the epilogue above (deterministic).
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page4[16];
 
@@ -792,17 +791,11 @@ bool tiles_ok(const VuGemmFwd& p) {
   return p.ncol % BN == 0 && g.H % PP<BN>::TH == 0 && g.W % PP<BN>::TW == 0;
 }
 
-int g_min_blocks = 256;  // vu_gemm_set_tuning(VU_TUNE_V4_MIN_BLOCKS, ...)
-int g_splitk = 1;        // vu_gemm_set_tuning(VU_TUNE_V4_SPLITK, ...): 0 off, 1 auto, k >= 2 forced
-int g_pp_full = 1;       // VU_TUNE_PP_FULL: one phase per step (conv3x3_pp_kernel FULL; 0 = two halves)
-int g_pp_persist = 0;    // VU_TUNE_PP_PERSIST: persistent tile walk for 128/256-column tiles (PERS);
-                         // 1 = grids over one block per CU, k >= 2 = always, grid capped at k (tests)
-
 // Output-column tile the ping-pong kernel uses for this problem (0 = not served).
 int pick_bn(const VuGemmFwd& p) {
   const VuGather& g = p.a;
   const int64_t pix = (int64_t)g.N * g.H * g.W;
-  const int mb = g_min_blocks;
+  const int mb = tune(VU_TUNE_V4_MIN_BLOCKS);
   // at least ~one block per CU, else the v3 tiles (more, smaller blocks) win
   if (tiles_ok<256>(p) && (pix / 256) * (p.ncol / 256) >= mb) return 256;
   if (p.ncol % 256 != 0 && tiles_ok<128>(p) && (pix / 512) * (p.ncol / 128) >= mb) return 128;
@@ -818,49 +811,34 @@ struct Plan {
   int bn, ks;
 };
 
-// Tile and K-split.  A grid under one block per CU gets the widest column
-// tile that divides the output and the smallest split that reaches one block
-// per CU (down4: 128 256x256 tiles -> 2, its input gradient: 64 tiles -> 4;
-// the ResNet34 encoder's 64^2 / 32^2 levels: 64 512x128 / 32 256x256 tiles),
-// at least g_split_min_chunks 32-channel chunks per split.
-int g_split_min_chunks = 2;  // vu_gemm_set_tuning(VU_TUNE_V4_SPLIT_CHUNKS, ...)
-
-}  // namespace
-int gemm_fwd_v2_small(const VuGemmFwd& p, int dtype);  // gemm_fwd2.hip
-int gemm_fwd_v7_bm(const VuGemmFwd& p, int dtype);     // gemm_fwd7.hip
-int cu_count4() {  // compute units of the current device (persistent grid)
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-namespace {
-
 template <int BN>
 int64_t tile_count(const VuGemmFwd& p) {
   const VuGather& g = p.a;
   return (int64_t)g.N * (g.H / PP<BN>::TH) * (g.W / PP<BN>::TW) * (p.ncol / BN);
 }
 
+// Tile and K-split.  A grid under one block per CU gets the widest column
+// tile that divides the output and the smallest split that reaches one block
+// per CU (down4: 128 256x256 tiles -> 2, its input gradient: 64 tiles -> 4;
+// the ResNet34 encoder's 64^2 / 32^2 levels: 64 512x128 / 32 256x256 tiles),
+// at least VU_TUNE_V4_SPLIT_CHUNKS 32-channel chunks per split.
 Plan plan(const VuGemmFwd& p) {
   const VuGather& g = p.a;
   const int chunks = g.C / 32;
+  const int splitk = tune(VU_TUNE_V4_SPLITK), min_chunks = tune(VU_TUNE_V4_SPLIT_CHUNKS);
   Plan r{pick_bn(p), 1};
   if (r.bn) {
-    if (g_splitk >= 2) r.ks = g_splitk < chunks ? g_splitk : chunks;
+    if (splitk >= 2) r.ks = splitk < chunks ? splitk : chunks;
     return r;
   }
-  const int maxks = chunks / (g_split_min_chunks > 0 ? g_split_min_chunks : 1);
-  if (g_splitk == 0 || maxks < 2) return r;
+  const int maxks = chunks / (min_chunks > 0 ? min_chunks : 1);
+  if (splitk == 0 || maxks < 2) return r;
   // small grids the 128x64 v2 tiles fill go there -- unless K is long
   // (>= 512 input channels: the UNet down4 input gradient, 1024 -> 512 at
   // 32^2, ran 201 us on v2 tiles vs 80 us split 4 ways here, tools/enc_bench.py)
-  if (g_splitk == 1 && g.C < 512 && gemm_fwd_v2_small(p, VU_BF16)) return r;
+  if (splitk == 1 && g.C < 512 && gemm_fwd_v2_small(p, VU_BF16)) return r;
   // ... and those the small-grid kernel takes (gemm_fwd7.hip, VU_TUNE_V7)
-  if (g_splitk == 1 && gemm_fwd_v7_bm(p, VU_BF16)) return r;
+  if (splitk == 1 && gemm_fwd_v7_bm(p, VU_BF16)) return r;
   int bn = 0;
   int64_t blocks = 0;
   if (tiles_ok<256>(p)) {
@@ -878,8 +856,8 @@ Plan plan(const VuGemmFwd& p) {
     return r;
   }
   if (blocks < 16) return r;
-  int ks = (int)((g_min_blocks + blocks - 1) / blocks);
-  if (g_splitk >= 2) ks = g_splitk;
+  int ks = (int)((tune(VU_TUNE_V4_MIN_BLOCKS) + blocks - 1) / blocks);
+  if (splitk >= 2) ks = splitk;
   if (ks > maxks) ks = maxks;
   if (ks < 2) return r;
   return Plan{bn, ks};
@@ -888,6 +866,9 @@ Plan plan(const VuGemmFwd& p) {
 template <int BN>
 int launch(const VuGemmFwd& p, int ks, hipStream_t st) {
   const VuGather& g = p.a;
+  // VU_TUNE_PP_FULL: one phase per step (conv3x3_pp_kernel FULL; 0 = two halves);
+  // VU_TUNE_PP_PERSIST: persistent tile walk for 128/256-column tiles (PERS)
+  const int pp_full = tune(VU_TUNE_PP_FULL), pp_persist = tune(VU_TUNE_PP_PERSIST);
   const int64_t mt = (int64_t)g.N * (g.H / PP<BN>::TH) * (g.W / PP<BN>::TW);
   const int64_t tiles = mt * (p.ncol / BN);
   if (ks <= 1) {
@@ -902,7 +883,7 @@ int launch(const VuGemmFwd& p, int ks, hipStream_t st) {
     else if (p.bnb_part) {
       // (the 64-column tiles spill with the FULL step's extra fragments)
       if constexpr (BN != 64) {
-        if (g_pp_full)
+        if (pp_full)
           hipLaunchKernelGGL((conv3x3_pp_kernel<BN, false, true, false, true>), dim3((unsigned)tiles), dim3(512), 0, st,
                              q);
         else
@@ -913,13 +894,13 @@ int launch(const VuGemmFwd& p, int ks, hipStream_t st) {
     }
     else if (p.relu)
       hipLaunchKernelGGL((conv3x3_pp_kernel<BN, false, false, true>), dim3((unsigned)tiles), dim3(512), 0, st, q);
-    else if (BN != 64 && g_pp_full && (g_pp_persist >= 2 || (g_pp_persist == 1 && tiles > cu_count4()))) {
-      // persistent walk: one block per CU (g_pp_persist >= 2: the grid capped at that many blocks, tests)
-      const int64_t grid = g_pp_persist >= 2 ? (tiles < g_pp_persist ? tiles : g_pp_persist) : cu_count4();
+    else if (BN != 64 && pp_full && (pp_persist >= 2 || (pp_persist == 1 && tiles > cu_count()))) {
+      // persistent walk: one block per CU (pp_persist >= 2: the grid capped at that many blocks, tests)
+      const int64_t grid = pp_persist >= 2 ? (tiles < pp_persist ? tiles : pp_persist) : cu_count();
       hipLaunchKernelGGL((conv3x3_pp_kernel<BN, false, false, false, BN != 64, false, BN != 64>),
                          dim3((unsigned)grid), dim3(512), 0, st, q);
     }
-    else if (BN != 64 && g_pp_full)  // (BN = 64 FULL spills 11 VGPRs: up4.1 fwd 341 -> 389 us, profiles/r6z_ab_pp64_full.txt)
+    else if (BN != 64 && pp_full)  // (BN = 64 FULL spills 11 VGPRs: up4.1 fwd 341 -> 389 us, profiles/r6z_ab_pp64_full.txt)
       hipLaunchKernelGGL((conv3x3_pp_kernel<BN, false, false, false, BN != 64>), dim3((unsigned)tiles), dim3(512), 0,
                          st, q);
 
@@ -931,7 +912,7 @@ int launch(const VuGemmFwd& p, int ks, hipStream_t st) {
   if (!p.workspace) return (int)hipErrorInvalidValue;
   VuGemmFwd q = p;
   q.ksplit = ks;
-  if (BN == 256 && g_pp_full)  // (the 128-column split variant spills with the extra fragments)
+  if (BN == 256 && pp_full)  // (the 128-column split variant spills with the extra fragments)
     hipLaunchKernelGGL((conv3x3_pp_kernel<BN, true, false, false, BN == 256>), grid, dim3(512), 0, st, q);
   else
     hipLaunchKernelGGL((conv3x3_pp_kernel<BN, true, false>), grid, dim3(512), 0, st, q);
@@ -942,10 +923,7 @@ int launch(const VuGemmFwd& p, int ks, hipStream_t st) {
 
 bool operands_ok(const VuGemmFwd& p, int dtype) {
   const VuGather& g = p.a;
-  if (dtype != VU_BF16 || p.out_mode != 0) return false;
-  if (g.R != 3 || g.S != 3 || g.sy != 1 || g.sx != 1 || g.dy != 1 || g.dx != 1 || g.oy != -1 ||
-      g.ox != -1 || g.Hs != g.H || g.Ws != g.W)
-    return false;
+  if (dtype != VU_BF16 || p.out_mode != 0 || !same3x3(g)) return false;
   if (g.C % 32 != 0) return false;
   for (int t = 0; t < g.nsrc; ++t)
     if (g.cend[t] % 32 != 0 || g.stride[t] % 8 != 0) return false;
@@ -966,14 +944,14 @@ int gemm_fwd_v4_bm(const VuGemmFwd& p, int dtype) {
 
 // BatchNorm-backward partial row tile (128: one wave tile, or one finish
 // tile) when the ping-pong kernel serves the problem and its output is a
-// whole plain tensor (no accumulate, no channel offset), else 0.
+// whole plain tensor (no accumulate, no channel offset), else 0.  (The
+// VuGemmFwd.zbias instantiations emit none.)
 int gemm_fwd_v4_bnb_tile(const VuGemmFwd& p, int dtype) {
-  if (!gemm_fwd_v4_bm(p, dtype) || p.accumulate || p.out_coff != 0) return 0;
+  if (p.zbias || !gemm_fwd_v4_bm(p, dtype) || p.accumulate || p.out_coff != 0) return 0;
   if (p.bnb_xstride % 8 != 0) return 0;
   return 128;
 }
 
-// fp32 split-K slab bytes the ping-pong kernel needs for this problem (0 = none)
 // the deterministic split-K finish over p.ksplit fp32 slabs in p.workspace
 // (also used by the v2 small-grid split, gemm_fwd2.hip)
 int splitk_finish_launch(const VuGemmFwd& p, hipStream_t st) {
@@ -983,6 +961,7 @@ int splitk_finish_launch(const VuGemmFwd& p, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+// fp32 split-K slab bytes the ping-pong kernel needs for this problem (0 = none)
 int64_t gemm_fwd_v4_workspace(const VuGemmFwd& p, int dtype) {
   if (!operands_ok(p, dtype)) return 0;
   const Plan r = plan(p);
@@ -999,82 +978,3 @@ int gemm_fwd_v4_launch(const VuGemmFwd& p, hipStream_t st) {
     default: return (int)hipErrorInvalidValue;
   }
 }
-
-int conv_fp8_tune(int key, int value);     // conv_fp8.hip
-int gemm_stream_tune(int key, int value);  // gemm_stream.hip
-int gemm_fwd_v2_tune(int key, int value);  // gemm_fwd2.hip
-int gemm_fwd_v5_tune(int key, int value);  // gemm_fwd5.hip
-int gemm_fwd_v6_tune(int key, int value);  // gemm_fwd6.hip
-int gemm_fwd_v7_tune(int key, int value);  // gemm_fwd7.hip
-int gemm_wgrad_v3_tune(int key, int value);  // gemm_wgrad3.hip
-int gemm_wgrad_v2_tune(int key, int value);  // gemm_wgrad2.hip
-int bn_tune(int key, int value);           // bn.hip
-int attn_tune(int key, int value);         // attention.hip
-extern int g_tune_gen;                     // gemm_fwd.hip
-extern int g_tune_slab4;                   // gemm_wgrad.hip
-
-namespace {
-int g_tune_unsafe = 0;  // VU_TUNE_UNSAFE
-int g_xm_modes = 0;     // vu_gemm_experiment_modes()
-int xm_bit(int key) {
-  return key == VU_TUNE_V6_XM ? 1 : key == VU_TUNE_V7_XM ? 2 : key == VU_TUNE_FP8_XM ? 4 : 0;
-}
-int set_tuning(int key, int value);
-}  // namespace
-
-// Experiment modes (timing decompositions, several with wrong results by
-// design) are refused unless VU_TUNE_UNSAFE was set first, and
-// tracked so that a benchmark can refuse to report while one is active.
-extern "C" int vu_gemm_set_tuning(int key, int value) {
-  if (key == VU_TUNE_UNSAFE) {
-    g_tune_unsafe = value != 0;
-    return 0;
-  }
-  const int bit = xm_bit(key);
-  if (bit && value != 0 && !g_tune_unsafe) return (int)hipErrorInvalidValue;
-  const int r = set_tuning(key, value);
-  if (r == 0 && bit) g_xm_modes = value != 0 ? (g_xm_modes | bit) : (g_xm_modes & ~bit);
-  return r;
-}
-
-extern "C" int vu_gemm_experiment_modes(void) { return g_xm_modes; }
-
-namespace {
-int set_tuning(int key, int value) {
-  if (key == VU_TUNE_V4_MIN_BLOCKS) {
-    g_min_blocks = value;
-    return 0;
-  }
-  if (key == VU_TUNE_V4_SPLITK) {
-    g_splitk = value;
-    return 0;
-  }
-  if (key == VU_TUNE_PP_FULL) {
-    g_pp_full = value;
-    return 0;
-  }
-  if (key == VU_TUNE_PP_PERSIST) {
-    g_pp_persist = value;
-    return 0;
-  }
-  if (key == VU_TUNE_V4_SPLIT_CHUNKS) {
-    g_split_min_chunks = value;
-    return 0;
-  }
-  if (key == VU_TUNE_GEN) {
-    if (value < 1 || value > 4) return (int)hipErrorInvalidValue;
-    g_tune_gen = value;
-    return 0;
-  }
-  if (key == VU_TUNE_SLAB4) {
-    g_tune_slab4 = value;
-    return 0;
-  }
-  if (conv_fp8_tune(key, value) == 0 || gemm_stream_tune(key, value) == 0 || gemm_fwd_v2_tune(key, value) == 0 ||
-      gemm_fwd_v5_tune(key, value) == 0 || gemm_fwd_v6_tune(key, value) == 0 || gemm_fwd_v7_tune(key, value) == 0 ||
-      gemm_wgrad_v3_tune(key, value) == 0 || gemm_wgrad_v2_tune(key, value) == 0 || bn_tune(key, value) == 0 ||
-      attn_tune(key, value) == 0)
-    return 0;
-  return (int)hipErrorInvalidValue;
-}
-}  // namespace

@@ -22,8 +22,7 @@
 //   * accumulate (input gradients): the old output values are loaded at the
 //     start of the tile's last step, before the next stage's DMA, so waiting
 //     for them does not drain the ring.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 static __device__ __attribute__((aligned(16))) uint32_t v5_zero_page[16];
 
@@ -318,24 +317,13 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p) {
   }
 }
 
-int cu_count5() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
-int g_v5 = 1;  // VU_TUNE_V5: 0 off, 1 on, k >= 2 on with the grid capped at k (tests)
-
 template <int BN, bool STATS, bool ACC>
 int launch5(const VuGemmFwd& p, hipStream_t st) {
   const int64_t M = (int64_t)p.a.N * p.a.H * p.a.W;
   const int64_t T = (M / BM) * (p.ncol / BN);
-  int64_t grid = T < cu_count5() ? T : cu_count5();
-  if (g_v5 >= 2 && grid > g_v5) grid = g_v5;
+  int64_t grid = T < cu_count() ? T : cu_count();
+  const int cap = tune(VU_TUNE_V5);  // 0 off, 1 on, k >= 2 on with the grid capped at k (tests)
+  if (cap >= 2 && grid > cap) grid = cap;
   if (p.relu)
     hipLaunchKernelGGL((gemm_fwd_v5_kernel<BN, STATS, ACC, true>), dim3((unsigned)grid), dim3(NT), 0, st, p);
   else
@@ -352,13 +340,11 @@ int launch_bn(const VuGemmFwd& p, hipStream_t st) {
 
 }  // namespace
 
-int gemm_fwd_v2_bm(const VuGemmFwd& p, int dtype);  // gemm_fwd2.hip (shared eligibility)
-
 // Statistics row tile (64) when v5 serves this problem, else 0: every v2
-// problem with whole 256-row tiles, 64 / 128-multiple column counts, a
-// 32-bit pixel count and at least 2 K steps.
+// problem (gemm_fwd_v2_bm: shared eligibility) with whole 256-row tiles, 64 /
+// 128-multiple column counts, a 32-bit pixel count and at least 2 K steps.
 int gemm_fwd_v5_bm(const VuGemmFwd& p, int dtype) {
-  if (g_v5 == 0 || gemm_fwd_v2_bm(p, dtype) == 0) return 0;
+  if (tune(VU_TUNE_V5) == 0 || gemm_fwd_v2_bm(p, dtype) == 0) return 0;
   const VuGather& g = p.a;
   const int64_t M = (int64_t)g.N * g.H * g.W;
   if (M % BM != 0 || M >= ((int64_t)1 << 31)) return 0;
@@ -374,12 +360,4 @@ int gemm_fwd_v5_bm(const VuGemmFwd& p, int dtype) {
 int gemm_fwd_v5_launch(const VuGemmFwd& p, hipStream_t st) {
   if (p.ncol == 64) return launch_bn<64>(p, st);
   return launch_bn<128>(p, st);
-}
-
-int gemm_fwd_v5_tune(int key, int value) {
-  if (key == VU_TUNE_V5) {
-    g_v5 = value < 0 ? 0 : value;
-    return 0;
-  }
-  return -1;
 }

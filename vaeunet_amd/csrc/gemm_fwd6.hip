@@ -30,8 +30,7 @@
 //     their 16-byte pieces with wswz(row); halo pixel P keeps its piece k at
 //     position (k + 2 * ((P >> 2) & 1)) & 3, which spreads the 16 lanes of
 //     every ds_read_b128 lane group over distinct banks for any tap shift.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 static __device__ __attribute__((aligned(16))) uint32_t v6_zero_page[16];
 
@@ -618,29 +617,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64s_kernel(VuGemmFwd p) {
   if (ntile_blk > 0) heavy(t - G);
 }
 
-int cu_count6() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
-int g_v6_xm = 0;  // VU_TUNE_V6_XM (experiment modes of conv3x3_c64_kernel)
-int g_v6_stag = 1;  // VU_TUNE_V6_STAG: 1 = the staggered-epilogue kernel (conv3x3_c64s_kernel)
-int g_v6 = 1;  // VU_TUNE_V6: 0 off, 1 on (grids of >= 1 tile per CU), k >= 2 on with the grid capped at k
-
 }  // namespace
 
-// Statistics row tile (64) when v6 serves this problem, else 0.
+// Statistics row tile (64) when v6 serves this problem, else 0.  VU_TUNE_V6:
+// 0 off, 1 on (grids of >= 1 tile per CU), k >= 2 on with the grid capped at k.
 int gemm_fwd_v6_bm(const VuGemmFwd& p, int dtype) {
-  if (g_v6 == 0 || dtype != VU_BF16 || p.out_mode != 0 || p.accumulate) return 0;
+  const int v6 = tune(VU_TUNE_V6);
+  if (v6 == 0 || dtype != VU_BF16 || p.out_mode != 0 || p.accumulate) return 0;
   const VuGather& g = p.a;
-  if (g.R != 3 || g.S != 3 || g.sy != 1 || g.sx != 1 || g.dy != 1 || g.dx != 1 || g.oy != -1 || g.ox != -1 ||
-      g.Hs != g.H || g.Ws != g.W)
-    return 0;
+  if (!same3x3(g)) return 0;
   if (g.nsrc != 1 || g.C != 64 || g.cend[0] != 64) return 0;
   // wider outputs without statistics (the input gradient of a 128 -> 64 concat
   // conv, up4.1: 64 -> 128 channels at 512^2) as one launch per 64-column
@@ -654,25 +639,20 @@ int gemm_fwd_v6_bm(const VuGemmFwd& p, int dtype) {
   const int64_t T = M / (TH * TW);
   // at least one tile per block (ResNet34 layer1: 64 -> 64 at 128^2, B = 8:
   // 256 tiles, 3-4 % faster per launch than the v3 halo kernel; round 5)
-  if (g_v6 == 1 && T < (int64_t)cu_count6()) return 0;
+  if (v6 == 1 && T < (int64_t)cu_count()) return 0;
   return 64;
 }
 
-// BatchNorm-backward partials are not emitted here (0): at 512^2 with 64
+// BatchNorm-backward partials are not emitted here: at 512^2 with 64
 // channels this kernel already moves ~3.7 TB/s, and reading the BN input in
 // its epilogue (+268 MB per launch) plus the partial sums cost more than the
 // separate reduction pass they replace (measured: +100 us per launch against
 // the 97 us pass; profiles/r3_prof_bnb_fusion.txt).
-int gemm_fwd_v6_bnb_tile(const VuGemmFwd& p, int dtype) {
-  (void)p;
-  (void)dtype;
-  return 0;
-}
-
 int gemm_fwd_v6_launch(const VuGemmFwd& p, hipStream_t st) {
   const int64_t T = (int64_t)p.a.N * p.a.H * p.a.W / (TH * TW);
-  int64_t grid = T < cu_count6() ? T : cu_count6();
-  if (g_v6 >= 2 && grid > g_v6) grid = g_v6;
+  const int v6 = tune(VU_TUNE_V6), xm = tune(VU_TUNE_V6_XM);  // (xm: experiment modes of conv3x3_c64_kernel)
+  int64_t grid = T < cu_count() ? T : cu_count();
+  if (v6 >= 2 && grid > v6) grid = v6;
   if (p.bnb_part) return (int)hipErrorInvalidValue;
   if (p.ncol > 64) {
     // one launch per 64-column slice: weight rows and output channels offset
@@ -685,7 +665,7 @@ int gemm_fwd_v6_launch(const VuGemmFwd& p, hipStream_t st) {
     }
     return 0;
   }
-  if (g_v6_stag && g_v6_xm == 0) {
+  if (tune(VU_TUNE_V6_STAG) && xm == 0) {  // the staggered-epilogue kernel (conv3x3_c64s_kernel)
     if (p.stat_sum) {
       if (p.relu) hipLaunchKernelGGL((conv3x3_c64s_kernel<true, true>), dim3((unsigned)grid), dim3(512), 0, st, p);
       else hipLaunchKernelGGL(conv3x3_c64s_kernel<true>, dim3((unsigned)grid), dim3(512), 0, st, p);
@@ -697,36 +677,19 @@ int gemm_fwd_v6_launch(const VuGemmFwd& p, hipStream_t st) {
   }
   if (p.stat_sum)
     if (p.relu) hipLaunchKernelGGL((conv3x3_c64_kernel<true, true>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 1) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 1>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 2) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 2>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 3) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 3>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 4) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 4>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 5) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 5>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 1) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 1>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 2) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 2>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 3) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 3>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 4) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 4>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 5) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false, 5>), dim3((unsigned)grid), dim3(512), 0, st, p);
     else hipLaunchKernelGGL(conv3x3_c64_kernel<true>, dim3((unsigned)grid), dim3(512), 0, st, p);
   else
     if (p.relu) hipLaunchKernelGGL((conv3x3_c64_kernel<false, true>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 1) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 1>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 2) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 2>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 3) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 3>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 4) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 4>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else if (g_v6_xm == 5) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 5>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 1) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 1>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 2) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 2>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 3) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 3>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 4) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 4>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    else if (xm == 5) hipLaunchKernelGGL((conv3x3_c64_kernel<false, false, 5>), dim3((unsigned)grid), dim3(512), 0, st, p);
     else hipLaunchKernelGGL(conv3x3_c64_kernel<false>, dim3((unsigned)grid), dim3(512), 0, st, p);
   return (int)hipGetLastError();
-}
-
-int gemm_fwd_v6_tune(int key, int value) {
-  if (key == VU_TUNE_V6_XM) {
-    if (value < 0 || value > 5) return (int)hipErrorInvalidValue;
-    g_v6_xm = value;
-    return 0;
-  }
-  if (key == VU_TUNE_V6) {
-    g_v6 = value < 0 ? 0 : value;
-    return 0;
-  }
-  if (key == VU_TUNE_V6_STAG) {
-    g_v6_stag = value != 0;
-    return 0;
-  }
-  return -1;
 }

@@ -37,8 +37,7 @@
 //     whole pixel rows staged through LDS; or (SPLIT) the fp32 tile to a
 //     split-K slab for splitk_finish_kernel (gemm_fwd4.hip), for the 16^2
 //     level whose 128 tiles are half a chip.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page7[16];
 // XM 5 (timing diagnostic): per wave of blocks < SG_DBG_BLOCKS, cycle totals of
@@ -477,9 +476,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_sg_kernel(VuGemmFwd p) {
   }
 }
 
-int g_v7 = 1;      // vu_gemm_set_tuning(VU_TUNE_V7, ...): 0 off, 1 auto, 2 every small grid incl. C >= 512
-int g_v7_nbw = 3;  // VU_TUNE_V7_NBW: weight ring slots (tap rows: 3 or 4; 3 measured 2-4 % faster)
-int g_v7_xm = 0;   // VU_TUNE_V7_XM: experiment mode of unsplit 6-slot launches (A/B runs only)
+// VU_TUNE_V7: 0 off, 1 auto, 2 every small grid incl. C >= 512
+// VU_TUNE_V7_NBW: weight ring slots (tap rows: 3 or 4; 3 measured 2-4 % faster)
+// VU_TUNE_V7_XM: experiment mode of unsplit 6-slot launches (A/B runs only)
 
 struct Plan7 {
   int tw, bn, ks;
@@ -488,10 +487,7 @@ struct Plan7 {
 Plan7 plan7(const VuGemmFwd& p, int dtype) {
   Plan7 r{0, 0, 0};
   const VuGather& g = p.a;
-  if (g_v7 == 0 || dtype != VU_BF16 || p.out_mode != 0) return r;
-  if (g.R != 3 || g.S != 3 || g.sy != 1 || g.sx != 1 || g.dy != 1 || g.dx != 1 || g.oy != -1 || g.ox != -1 ||
-      g.Hs != g.H || g.Ws != g.W)
-    return r;
+  if (tune(VU_TUNE_V7) == 0 || dtype != VU_BF16 || p.out_mode != 0 || !same3x3(g)) return r;
   if (g.C % 64 != 0 || p.ncol % 64 != 0) return r;
   for (int t = 0; t < g.nsrc; ++t)
     if (g.cend[t] % 32 != 0 || g.stride[t] % 8 != 0) return r;
@@ -520,19 +516,20 @@ int launch7(const VuGemmFwd& p, const Plan7& r, hipStream_t st) {
   q.ksplit = r.ks;
   const dim3 gr((unsigned)(r.ks <= 1 ? tiles : tiles * r.ks));
   if (r.ks > 1 && !p.workspace) return (int)hipErrorInvalidValue;
-  if (r.ks <= 1 && g_v7_xm == 2)
+  const int xm = tune(VU_TUNE_V7_XM), nbw = tune(VU_TUNE_V7_NBW);
+  if (r.ks <= 1 && xm == 2)
     hipLaunchKernelGGL((conv3x3_sg_kernel<TW, 64, 4, false, 2>), gr, dim3(512), 0, st, q);
-  else if (r.ks <= 1 && g_v7_xm == 4)
+  else if (r.ks <= 1 && xm == 4)
     hipLaunchKernelGGL((conv3x3_sg_kernel<TW, 64, 4, false, 4>), gr, dim3(512), 0, st, q);
-  else if (r.ks <= 1 && g_v7_xm == 5 && !p.relu)
+  else if (r.ks <= 1 && xm == 5 && !p.relu)
     hipLaunchKernelGGL((conv3x3_sg_kernel<TW, 64, 3, false, 5>), gr, dim3(512), 0, st, q);
   else if (r.ks <= 1 && p.relu)
     hipLaunchKernelGGL((conv3x3_sg_kernel<TW, 64, 3, false, 0, true>), gr, dim3(512), 0, st, q);
-  else if (r.ks <= 1 && g_v7_nbw == 3)
+  else if (r.ks <= 1 && nbw == 3)
     hipLaunchKernelGGL((conv3x3_sg_kernel<TW, 64, 3, false>), gr, dim3(512), 0, st, q);
   else if (r.ks <= 1)
     hipLaunchKernelGGL((conv3x3_sg_kernel<TW, 64, 4, false>), gr, dim3(512), 0, st, q);
-  else if (g_v7_nbw == 3)
+  else if (nbw == 3)
     hipLaunchKernelGGL((conv3x3_sg_kernel<TW, 64, 3, true>), gr, dim3(512), 0, st, q);
   else
     hipLaunchKernelGGL((conv3x3_sg_kernel<TW, 64, 4, true>), gr, dim3(512), 0, st, q);
@@ -540,8 +537,6 @@ int launch7(const VuGemmFwd& p, const Plan7& r, hipStream_t st) {
 }
 
 }  // namespace
-
-int splitk_finish_launch(const VuGemmFwd& p, hipStream_t st);  // gemm_fwd4.hip
 
 // Row tile (128) when the small-grid kernel serves this problem, else 0.  It
 // is asked only after the resident-weight (v6) and unsplit ping-pong (v4)
@@ -551,7 +546,7 @@ int gemm_fwd_v7_bm(const VuGemmFwd& p, int dtype) {
   const Plan7 r = plan7(p, dtype);
   if (!r.tw) return 0;
   // >= 512 input channels on 32-wide images: the v4 split-K measured faster
-  if (g_v7 == 1 && p.a.C >= 512 && r.tw == 32) return 0;
+  if (tune(VU_TUNE_V7) == 1 && p.a.C >= 512 && r.tw == 32) return 0;
   return 128;
 }
 
@@ -576,22 +571,4 @@ int gemm_fwd_v7_launch(const VuGemmFwd& p, hipStream_t st) {
 extern "C" int vu_sg_debug_read(unsigned long long* out, int n) {
   if (n > SG_DBG_BLOCKS * 64) n = SG_DBG_BLOCKS * 64;
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(vu_sg_dbg), (size_t)n * sizeof(unsigned long long));
-}
-
-int gemm_fwd_v7_tune(int key, int value) {
-  if (key == VU_TUNE_V7) {
-    if (value < 0 || value > 2) return (int)hipErrorInvalidValue;
-    g_v7 = value;
-    return 0;
-  }
-  if (key == VU_TUNE_V7_XM) {
-    g_v7_xm = value;
-    return 0;
-  }
-  if (key == VU_TUNE_V7_NBW) {
-    if (value != 3 && value != 4) return (int)hipErrorInvalidValue;
-    g_v7_nbw = value;
-    return 0;
-  }
-  return -1;
 }

@@ -19,8 +19,7 @@
 //     owns 4*GS consecutive output columns of one pixel (16/32-byte stores,
 //     the ConvT pixel shuffle keeps them contiguous), BN partials per wave
 //     tile by DPP row sums, optional accumulate (input gradients).
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
 
@@ -264,16 +263,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_stream_kernel(VuGemmFwd p) {
   }
 }
 
-int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 // pixel fragments per wave tile: NF*NJ <= 16 accumulator fragments, NF*KS <= 8 operand registers sets
 constexpr int nf_of(int ks, int nj) {
   return (16 / nj < 4 ? 16 / nj : 4) < (8 / ks) ? (16 / nj < 4 ? 16 / nj : 4) : 8 / ks;
@@ -305,8 +294,6 @@ int launch_ks(const VuGemmFwd& p, hipStream_t st) {
   }
 }
 
-bool g_enabled = true;  // VU_TUNE_STREAM
-
 }  // namespace
 
 // Row tile (16*NF pixels) when the stream kernel serves this problem, else 0:
@@ -315,7 +302,7 @@ bool g_enabled = true;  // VU_TUNE_STREAM
 // (mode 1, no statistics) output, whole tiles, enough tiles to fill the chip.
 int gemm_stream_bm(const VuGemmFwd& p, int dtype) {
   const VuGather& g = p.a;
-  if (!g_enabled || dtype != VU_BF16) return 0;
+  if (!tune(VU_TUNE_STREAM) || dtype != VU_BF16) return 0;
   if (g.R != 1 || g.S != 1 || g.sy != 1 || g.sx != 1 || g.oy != 0 || g.ox != 0 || g.Hs != g.H ||
       g.Ws != g.W || g.nsrc != 1)
     return 0;
@@ -343,12 +330,4 @@ int gemm_stream_launch(const VuGemmFwd& p, hipStream_t st) {
     case 128: return launch_ks<4>(p, st);
     default: return (int)hipErrorInvalidValue;
   }
-}
-
-int gemm_stream_tune(int key, int value) {
-  if (key == VU_TUNE_STREAM) {
-    g_enabled = value != 0;
-    return 0;
-  }
-  return -1;
 }

@@ -15,8 +15,7 @@
 // ds_read_b32 per operand (lanes on consecutive columns, rows padded).
 // Split-K over m writes fp32 slabs, reduced in a fixed order (deterministic).
 #include <stdlib.h>
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
 
@@ -393,26 +392,26 @@ void launch_slab4(const float* slab, int splits, int ni, int nj, int C, int cval
                      ni, nj, C, cvalid, s_i, s_tap, s_c, out, accumulate);
 }
 
-}  // namespace
-
-int gemm_wgrad_v2_tile(const VuGemmWgrad& p, int dtype, int* bi, int* bj);
-int gemm_wgrad_v2_launch(const VuGemmWgrad& p, hipStream_t st);
-int gemm_wgrad_v3_tile(const VuGemmWgrad& p, int dtype, int* bi, int* bj);
-int gemm_wgrad_v3_launch(const VuGemmWgrad& p, hipStream_t st);
-
-extern int g_tune_gen;  // gemm_fwd.hip (VU_TUNE_GEN)
-static bool use_v2w(int dtype) { return g_tune_gen >= 2 && dtype == VU_BF16; }
-static bool use_v3w(int dtype) { return g_tune_gen >= 3 && use_v2w(dtype); }
-
-// Output tile the dispatcher will use (host split-K heuristic).  Returns the
-// kernel generation: 3 = halo kernel (splits must be whole 128-pixel tiles),
-// 2 = large-tile LDS-DMA kernel, 1 = register-staged kernel.
-extern "C" int vu_gemm_wgrad_tile(const VuGemmWgrad* args, int dtype, int* bi, int* bj) {
-  if (use_v3w(dtype) && gemm_wgrad_v3_tile(*args, dtype, bi, bj)) return 3;
-  if (use_v2w(dtype) && gemm_wgrad_v2_tile(*args, dtype, bi, bj)) return 2;
-  *bi = args->ni <= 64 ? 64 : 128;
+// The kernel generation that runs this problem, in dispatch order, and its
+// output tile: 3 = halo kernel, 2 = large-tile LDS-DMA kernel, 1 = the
+// register-staged kernel of this file (VU_TUNE_GEN caps it; above 1: bf16).
+// launching: the halo kernel runs only splits of whole 128-pixel tiles.  The
+// tile query does not ask that: callers choose the split from its answer.
+int pick(const VuGemmWgrad& p, int dtype, int* bi, int* bj, bool launching) {
+  const int gen = dtype == VU_BF16 ? tune(VU_TUNE_GEN) : 1;
+  if (gen >= 3 && !(launching && p.m_per_split % 128 != 0) && gemm_wgrad_v3_tile(p, dtype, bi, bj)) return 3;
+  if (gen >= 2 && gemm_wgrad_v2_tile(p, dtype, bi, bj)) return 2;
+  *bi = p.ni <= 64 ? 64 : 128;
   *bj = 128;
   return 1;
+}
+
+}  // namespace
+
+// Output tile the dispatcher will use (host split-K heuristic).  Returns the
+// kernel generation (splits for 3 must be whole 128-pixel tiles).
+extern "C" int vu_gemm_wgrad_tile(const VuGemmWgrad* args, int dtype, int* bi, int* bj) {
+  return pick(*args, dtype, bi, bj, false);
 }
 
 extern "C" int vu_gemm_wgrad(const VuGemmWgrad* args, int dtype, void* stream) {
@@ -427,21 +426,20 @@ extern "C" int vu_gemm_wgrad(const VuGemmWgrad* args, int dtype, void* stream) {
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   int bi, bj;
-  if (use_v3w(dtype) && args->m_per_split % 128 == 0 && gemm_wgrad_v3_tile(*args, dtype, &bi, &bj))
-    return gemm_wgrad_v3_launch(*args, st);
-  if (use_v2w(dtype) && gemm_wgrad_v2_tile(*args, dtype, &bi, &bj)) return gemm_wgrad_v2_launch(*args, st);
-  return dtype == VU_BF16 ? dispatch_wg<bf16_t>(*args, st) : dispatch_wg<float>(*args, st);
+  switch (pick(*args, dtype, &bi, &bj, true)) {
+    case 3: return gemm_wgrad_v3_launch(*args, st);
+    case 2: return gemm_wgrad_v2_launch(*args, st);
+    default: return dtype == VU_BF16 ? dispatch_wg<bf16_t>(*args, st) : dispatch_wg<float>(*args, st);
+  }
 }
-
-int g_tune_slab4 = 1;  // VU_TUNE_SLAB4 = 0: the scalar slab reduce (A/B runs)
-static bool slab4_on() { return g_tune_slab4 != 0; }
 
 extern "C" int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C, int cvalid, int64_t s_i,
                               int64_t s_tap, int64_t s_c, float* out, int accumulate, void* stream) {
   int64_t tot = (int64_t)ni * nj;
   if (tot == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (tot % 4 == 0 && reinterpret_cast<uintptr_t>(slab) % 16 == 0 && slab4_on()) {
+  if (tot % 4 == 0 && reinterpret_cast<uintptr_t>(slab) % 16 == 0 && tune(VU_TUNE_SLAB4) != 0) {
+    // (VU_TUNE_SLAB4 = 0: the scalar slab reduce below, A/B runs)
     // split lanes: about 4 slab loads per lane, at most 16 lanes
     if (splits >= 64) launch_slab4<16>(slab, splits, ni, nj, C, cvalid, s_i, s_tap, s_c, out, accumulate, st);
     else if (splits >= 32) launch_slab4<8>(slab, splits, ni, nj, C, cvalid, s_i, s_tap, s_c, out, accumulate, st);

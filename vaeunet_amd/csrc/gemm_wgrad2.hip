@@ -11,8 +11,7 @@
 //     ds_read_b64_tr_b16 fragment reads conflict-free is applied to the
 //     SOURCE column of each lane (the LDS image stays lane-linear);
 //   * deterministic split-K over pixels into fp32 slabs (vu_slab_reduce).
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page[16];  // per code object
 
@@ -342,18 +341,9 @@ int launch(const VuGemmWgrad& p, hipStream_t st) {
 // for the large 1x1 / ConvT weight gradients (both dims >= 256): 1.5x the
 // MFMA work per LDS byte of the 128 x 256 tile, whose blocks wait on the
 // L2 -> LDS feed (~16 GB/s per CU on the UNet ConvT gradients)
-int g_w2_big = 0;
-bool big_tile(const VuGemmWgrad& p) { return g_w2_big && p.ni >= 256 && p.nj >= 256; }
+bool big_tile(const VuGemmWgrad& p) { return tune(VU_TUNE_W2_BIG) && p.ni >= 256 && p.nj >= 256; }
 
 }  // namespace
-
-int gemm_wgrad_v2_tune(int key, int value) {
-  if (key == VU_TUNE_W2_BIG) {
-    g_w2_big = value;
-    return 0;
-  }
-  return -1;
-}
 
 // Output tile (BI, BJ) of the v2 kernel for this problem, or 0 if it does not apply.
 int gemm_wgrad_v2_tile(const VuGemmWgrad& p, int dtype, int* bi, int* bj) {

@@ -21,8 +21,7 @@
 //     double-buffered per pixel tile; fp32 accumulators stay in registers
 //     across the split, then one slab write (vu_slab_reduce sums the splits in
 //     a fixed order: deterministic).
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page_w3[16];
 
@@ -361,12 +360,11 @@ int launch(const VuGemmWgrad& p, hipStream_t st) {
 // Output-channel tile: 128 unless the grid is small -- fewer than 256 blocks
 // even at the finest split (4 pixel tiles per block) -- where 64-channel tiles
 // double the blocks (the ResNet34 encoder's 64^2 / 32^2 / 16^2 levels: 128
-// blocks, half the chip, with 128-channel tiles)
-int g_w3_small = 1;  // vu_gemm_set_tuning(VU_TUNE_W3_SMALL, ...): 0 = round-2 behaviour (A/B runs)
-
+// blocks, half the chip, with 128-channel tiles).  VU_TUNE_W3_SMALL = 0: the
+// round-2 behaviour (A/B runs).
 int pick_bi(const VuGemmWgrad& p) {
   if (p.ni <= 64 || p.q.W % 32 != 0) return 64;  // (128 x 16-wide tiles would spill)
-  if (!g_w3_small) return 128;
+  if (!tune(VU_TUNE_W3_SMALL)) return 128;
   const int64_t T = (int64_t)p.q.N * p.q.H * p.q.W / TP;
   const int64_t blocks128 = (int64_t)((p.ni + 127) / 128) * (p.q.C / 64) * (T / 4 > 0 ? T / 4 : 1);
   return blocks128 < 256 ? 64 : 128;
@@ -386,13 +384,11 @@ int gemm_wgrad_v3_tile(const VuGemmWgrad& p, int dtype, int* bi, int* bj) {
   if (a.nsrc != 1 || a.R != 1 || a.S != 1 || a.oy != 0 || a.ox != 0 || a.stride[0] % 8 || a.C != p.ni ||
       p.ni % 8)
     return 0;
-  if (g.R != 3 || g.S != 3 || g.sy != 1 || g.sx != 1 || g.dy != 1 || g.dx != 1 || g.oy != -1 || g.ox != -1 ||
-      g.Hs != g.H || g.Ws != g.W || a.N != g.N || a.H != g.H || a.W != g.W)
-    return 0;
+  if (!same3x3(g) || a.N != g.N || a.H != g.H || a.W != g.W) return 0;
   if (g.C % 64 || p.nj != 9 * g.C) return 0;
   for (int t = 0; t < g.nsrc; ++t)
     if (g.cend[t] % 64 || g.stride[t] % 8) return 0;
-  const int tw = g.W % 32 == 0 ? 32 : (g.W % 16 == 0 && g_w3_small ? 16 : 0);
+  const int tw = g.W % 32 == 0 ? 32 : (g.W % 16 == 0 && tune(VU_TUNE_W3_SMALL) ? 16 : 0);
   if (!tw || g.H % (TP / tw)) return 0;
   if ((int64_t)g.N * g.H * g.W >= (int64_t)1 << 31) return 0;
   if ((int64_t)(TP / tw) * g.W * a.stride[0] >= (int64_t)1 << 31) return 0;   // 32-bit dy slot offsets
@@ -408,12 +404,4 @@ int gemm_wgrad_v3_launch(const VuGemmWgrad& p, hipStream_t st) {
   if (p.q.W % 32 != 0) return launch<64, 16>(p, st);
   if (pick_bi(p) == 64) return launch<64, 32>(p, st);
   return launch<128, 32>(p, st);
-}
-
-int gemm_wgrad_v3_tune(int key, int value) {
-  if (key == VU_TUNE_W3_SMALL) {
-    g_w3_small = value != 0;
-    return 0;
-  }
-  return -1;
 }

@@ -27,8 +27,7 @@
 //                      backward, both heads' backward -> dpooled (the caller
 //                      broadcasts dpooled / HW into d f[-1] with
 //                      vu_sample_broadcast).
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
 
@@ -552,7 +551,7 @@ __global__ __launch_bounds__(LB_T) void latent_bwd_heads_kernel(VuLatentHeads hb
 #define DISPATCH_T(dtype, ...) \
   if ((dtype) == VU_BF16) { using T = bf16_t; __VA_ARGS__; } else { using T = float; __VA_ARGS__; }
 
-static bool pow2_ok(int C) { int v = C / 8; return C % 8 == 0 && v > 0 && v <= 256 && (v & (v - 1)) == 0; }
+static bool pow2_ok(int C) { return C % 8 == 0 && pow2(C / 8) && C / 8 <= 256; }
 
 extern "C" int vu_vae_heads_fwd(const void* f4, int64_t fs, int N, int HW, int C, const float* w_mu,
                                 const float* b_mu, const float* w_lv, const float* b_lv, int L, const float* eps,

@@ -6,17 +6,9 @@
 // All NHWC, 8 channels (16 B bf16 / 32 B fp32) per thread where the channel
 // count allows, grid-stride loops.  Backward passes are gathers (each output
 // element written exactly once, no atomics) so results are deterministic.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
-
-inline unsigned ew_grid(int64_t work) {
-  int64_t g = (work + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
 
 // ------------------------------ max pool --------------------------------
 // PyTorch CPU/GPU max_pool2d scan: window row-major, update when

@@ -10,17 +10,9 @@
 //     exact broadcast of the per-sample vector (unet_resnet.py:217-221, 93)
 //
 // NHWC, fixed-channel 8-wide vectors, deterministic reductions.
-#include "common.h"
-#include "../../include/vaeunet.h"
+#include "host.h"
 
 namespace {
-
-inline unsigned ew_grid(int64_t work) {
-  int64_t g = (work + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
 
 // ---- max pool 3x3, stride 2, pad 1 (records the window argmax 0..8) ----
 template <typename T>
@@ -257,7 +249,6 @@ __global__ void reparam_bwd(const float* lv, const float* eps, const float* dz, 
   dlv[i] = accumulate ? dlv[i] + gl : gl;
 }
 
-inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 }  // namespace
 
