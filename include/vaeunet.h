@@ -542,7 +542,8 @@ int vu_attn_gate_fwd(const float* q, const float* st, const void* x,
                      int64_t xs, int64_t P, int C, float* pmap, void* out,
                      int64_t os, int dtype, void* stream);
 /* backward of out = x*p: dx_direct = dout*p (written to dx), and
- * dq_pre[p] = (sum_c dout*x) * p * (1-p)  (grad w.r.t. the BN(1) output) */
+ * dq_pre[p] = (sum_c dout*x) * p * (1-p)  (grad w.r.t. the BN(1) output).
+ * dx may be null: only dq_pre is written (vu_attn_tail_bwd forms dout*p). */
 int vu_attn_gate_bwd(const void* dout, int64_t dos, const void* x, int64_t xs,
                      const float* pmap, int64_t P, int C, void* dx,
                      int64_t dxs, float* dqpre, int dtype, void* stream);
@@ -570,6 +571,27 @@ int vu_attn_psi_bwd_bnb(const void* ug, const void* ux, int64_t P, int F,
                         float* workspace, const float* mean_g, const float* invstd_g,
                         const float* mean_x, const float* invstd_x, float* bnb_g,
                         float* bnb_x, int dtype, void* stream);
+/* (ds may be null there: it is not stored; the partials are unchanged.) */
+
+/* The rest of the gate backward as one stream over the pixels (bf16, F in
+ * {32, 64, 128}, C in {64, 128, 256}, P a multiple of vu_attn_tail_bwd_tile):
+ *   ds  = (s > 0) ? dq * wpsi : 0          as vu_attn_psi_bwd stores it
+ *   dug, dux = vu_bn_bwd_apply2(ds, ug, ux; mean_?, coef_?[3][F])   (stored, [P][F])
+ *   dg[p*dgs + dg_coff + c] (=|+=) sum_f dug[p,f] wdg[c*ldg + f]    (dg_acc: +=)
+ *   dx[p*dxs + c] = bf16(dout[p*dos + c] * pmap[p]) + sum_f dux[p,f] wdx[c*ldx + f]
+ * with the bits of vu_attn_gate_bwd, vu_attn_psi_bwd, vu_bn_bwd_apply2 and two
+ * accumulating vu_gemm_fwd calls.  wdg / wdx: the [C][F] input-gradient weight
+ * images.  _ok is about correctness only (no problem-size floor). */
+int64_t vu_attn_tail_bwd_tile(int F, int C);   /* pixels per wave tile, 0: not served */
+int vu_attn_tail_bwd_ok(int64_t P, int F, int C, int64_t ldg, int64_t ldx, int64_t dos,
+                        int64_t dgs, int64_t dg_coff, int64_t dxs, int dtype);
+int vu_attn_tail_bwd(const void* ug, const void* ux, const float* dq, int64_t P, int F, int C,
+                     const float* sg, const float* tg, const float* sx, const float* tx,
+                     const float* wpsi, const float* mean_g, const float* coef_g,
+                     const float* mean_x, const float* coef_x, const void* wdg, int64_t ldg,
+                     const void* wdx, int64_t ldx, const void* dout, int64_t dos,
+                     const float* pmap, void* dg, int64_t dgs, int64_t dg_coff, int dg_acc,
+                     void* dx, int64_t dxs, void* dug, void* dux, int dtype, void* stream);
 
 /* ---- 1x1 conv with a tiny output (OutConv unet_parts.py:97-103,
  *      final_conv unet_resnet.py:189) -------------------------------------- */

@@ -163,6 +163,10 @@ _SIGS = {
                                  _i, _p]),
     "vu_attn_psi_bwd": (_i, [_p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i,
                              _p]),
+    "vu_attn_tail_bwd_tile": (_l, [_i, _i]),
+    "vu_attn_tail_bwd_ok": (_i, [_l, _i, _i, _l, _l, _l, _l, _l, _l, _i]),
+    "vu_attn_tail_bwd": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _l,
+                              _p, _p, _l, _l, _i, _p, _l, _p, _p, _i, _p]),
     "vu_pointwise_fwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _l, _i, _p]),
     "vu_pointwise_bwd_workspace_bytes": (_l, [_l, _i, _i]),
     "vu_pointwise_bn_fwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _l, _i, _p]),

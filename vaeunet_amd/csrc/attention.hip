@@ -13,6 +13,7 @@
 // partial (sum, centered M2).  Weight-gradient sums use per-block partial
 // slabs reduced in a fixed order (deterministic, no float atomics).
 #include "host.h"
+#include "attn_pre.h"
 
 namespace {
 
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(256) void psi_fwd_u_kernel(const T* ug, const T* ux
       float acc = 0.f;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        float s = fmaxf(va[u].get(k) * wsg[k] + wtg[k] + vb[u].get(k) * wsx[k] + wtx[k], 0.f);
+        float s = fmaxf(attn_pre(va[u].get(k), wsg[k], wtg[k], vb[u].get(k), wsx[k], wtx[k]), 0.f);
         acc += wp[k] * s;
       }
       if (p >= P) acc = 0.f;
@@ -265,7 +266,7 @@ __global__ void gate_bwd_kernel(const T* dout, int64_t dos, const T* x, int64_t 
           acc += vd.get(k) * vx.get(k);
           vo.set(k, vd.get(k) * pv);
         }
-        vo.store(dx + p * dxs + c);
+        if (dx) vo.store(dx + p * dxs + c);
       }
     }
     acc = group_sum(acc, lpp);
@@ -274,8 +275,9 @@ __global__ void gate_bwd_kernel(const T* dout, int64_t dos, const T* x, int64_t 
 }
 
 // gate backward for C <= 512 (one 8-channel chunk per lane), U pixel rows of
-// loads in flight per lane
-template <typename T, int U>
+// loads in flight per lane.  DX = false: dx is not written (the fused
+// backward tail re-forms dout * p itself, attention_tail.hip)
+template <typename T, int U, bool DX = true>
 __global__ __launch_bounds__(256) void gate_bwd_u_kernel(const T* dout, int64_t dos, const T* x, int64_t xs,
                                                          const float* pmap, int64_t P, int C, T* dx, int64_t dxs,
                                                          float* dbnq) {
@@ -305,9 +307,10 @@ __global__ __launch_bounds__(256) void gate_bwd_u_kernel(const T* dout, int64_t 
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         acc += vd[u].get(k) * vx[u].get(k);
-        vo.set(k, vd[u].get(k) * pv[u]);
+        if constexpr (DX) vo.set(k, vd[u].get(k) * pv[u]);
       }
-      if (p < P) vo.store(dx + p * dxs + c);
+      if constexpr (DX)
+        if (p < P) vo.store(dx + p * dxs + c);
       acc = group_sum(acc, lpp);
       if (sub == 0 && p < P) dbnq[p] = acc * pv[u] * (1.f - pv[u]);
     }
@@ -326,7 +329,9 @@ constexpr int MAXB = 1024;
 // [block][2][F] (VuGemmFwd.bnb_part's layout), from the ug, ux and ds values
 // already in registers: the two separate reduction passes over ds, ug and
 // ds, ux are not run.
-template <typename T, int U, bool BNB = false>
+// DS = false: ds is not stored (the fused backward tail re-forms it); the
+// partials still use the rounded ds values.
+template <typename T, int U, bool BNB = false, bool DS = true>
 __global__ __launch_bounds__(256) void psi_bwd_u_kernel(const T* ug, const T* ux, int64_t P, int F, const float* sg,
                                                         const float* tg, const float* sx, const float* tx,
                                                         const float* wpsi, const float* dq, T* ds, float* part,
@@ -380,7 +385,7 @@ __global__ __launch_bounds__(256) void psi_bwd_u_kernel(const T* ug, const T* ux
         if (okp[u] && sub == 0) db += g[u];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          float s = va[u].get(k) * wsg[k] + wtg[k] + vb[u].get(k) * wsx[k] + wtx[k];
+          float s = attn_pre(va[u].get(k), wsg[k], wtg[k], vb[u].get(k), wsx[k], wtx[k]);
           bool on = s > 0.f;
           if (okp[u]) dw[k] += on ? g[u] * s : 0.f;
           o[u].set(k, on ? g[u] * wp[k] : 0.f);
@@ -395,9 +400,10 @@ __global__ __launch_bounds__(256) void psi_bwd_u_kernel(const T* ug, const T* ux
         }
         vec8_tie(o[u]);
       }
+      if constexpr (DS)
 #pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (okp[u]) o[u].store(ds + (p0 + w * ppw + slot + (it + u) * 4 * ppw) * F + c);
+        for (int u = 0; u < U; ++u)
+          if (okp[u]) o[u].store(ds + (p0 + w * ppw + slot + (it + u) * 4 * ppw) * F + c);
     }
   }
 #pragma unroll
@@ -774,9 +780,12 @@ extern "C" int vu_attn_gate_bwd(const void* dout, int64_t dos, const void* x, in
   hipStream_t st = (hipStream_t)stream;
   if (P == 0) return 0;
   DISPATCH_T(dtype, {
-    if (tune(VU_TUNE_ATTN) && C <= 512)
+    if (tune(VU_TUNE_ATTN) && C <= 512 && dx)
       hipLaunchKernelGGL((gate_bwd_u_kernel<T, 2>), dim3(ew_grid(P * 8)), dim3(256), 0, st, (const T*)dout, dos,
                          (const T*)x, xs, pmap, P, C, (T*)dx, dxs, dqpre);
+    else if (tune(VU_TUNE_ATTN) && C <= 512)
+      hipLaunchKernelGGL((gate_bwd_u_kernel<T, 2, false>), dim3(ew_grid(P * 8)), dim3(256), 0, st, (const T*)dout,
+                         dos, (const T*)x, xs, pmap, P, C, (T*)nullptr, dxs, dqpre);
     else
       hipLaunchKernelGGL((gate_bwd_kernel<T>), dim3(ew_grid(P * 8)), dim3(256), 0, st, (const T*)dout, dos,
                          (const T*)x, xs, pmap, P, C, (T*)dx, dxs, dqpre);
@@ -805,8 +814,14 @@ extern "C" int vu_attn_psi_bwd_bnb(const void* ug, const void* ux, int64_t P, in
   if (nblk == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, {
-    hipLaunchKernelGGL((psi_bwd_u_kernel<T, 4, true>), dim3(nblk), dim3(256), 0, st, (const T*)ug, (const T*)ux, P, F,
-                       sg, tg, sx, tx, wpsi, dq, (T*)ds, workspace, mean_g, invstd_g, mean_x, invstd_x, bnb_g, bnb_x);
+    if (ds)
+      hipLaunchKernelGGL((psi_bwd_u_kernel<T, 4, true>), dim3(nblk), dim3(256), 0, st, (const T*)ug, (const T*)ux, P,
+                         F, sg, tg, sx, tx, wpsi, dq, (T*)ds, workspace, mean_g, invstd_g, mean_x, invstd_x, bnb_g,
+                         bnb_x);
+    else
+      hipLaunchKernelGGL((psi_bwd_u_kernel<T, 4, true, false>), dim3(nblk), dim3(256), 0, st, (const T*)ug,
+                         (const T*)ux, P, F, sg, tg, sx, tx, wpsi, dq, (T*)nullptr, workspace, mean_g, invstd_g,
+                         mean_x, invstd_x, bnb_g, bnb_x);
   })
   hipLaunchKernelGGL(part_final, dim3((F + 1 + 31) / 32), dim3(COLSUM_THREADS), 0, st, workspace, nblk, F + 1, dwpsi,
                      F, dbpsi, accumulate);

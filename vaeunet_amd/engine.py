@@ -679,6 +679,27 @@ def down_bwd(M, mod, saved, dout, add=None):
 # Round 6: the attention psi backward emits the first backward-reduction
 # stage of the W_g and W_x BatchNorms (vu_attn_psi_bwd_bnb).  A/B switch.
 FUSE_ATTN_BN_REDUCE = True
+# Everything after the psi backward's reductions -- ds, both BatchNorm applies,
+# both 1x1 input gradients, the dout * psi term of dx -- as one stream over the
+# pixels (vu_attn_tail_bwd): ds and the first dx are never written, dug / dux
+# are written once and not read back by the input-gradient GEMMs.  A/B switch.
+FUSE_ATTN_TAIL = True
+# the fused tail is a persistent stream kernel: it serves a gate with at least
+# this many wave tiles per compute unit (the floor of the stream 1x1 GEMMs it
+# replaces; smaller gates keep the separate kernels)
+ATTN_TAIL_MIN_TILES_PER_CU = 8
+
+
+def _attn_tail_ok(M, P, F, g, x, dout, dg_out, wdg, wdx, dx):
+    if not FUSE_ATTN_TAIL or M.d != BF16 or dg_out is None or g.shape[1] != x.shape[1]:
+        return False
+    C_ = x.shape[1]
+    dst, coff = dg_out
+    if not K.query("vu_attn_tail_bwd_ok", P, F, C_, wdg.shape[-1], wdx.shape[-1], K.pstride(dout),
+                   K.pstride(dst), coff, K.pstride(dx), M.d):
+        return False
+    cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+    return P // K.query("vu_attn_tail_bwd_tile", F, C_) >= ATTN_TAIL_MIN_TILES_PER_CU * cus
 
 
 def attention_fwd(M, att, g, x):
@@ -731,35 +752,65 @@ def attention_bwd(M, att, saved, dout, dg_out, dg_acc):
     F = wg.out_channels
     dx = torch.empty_like(x)
     dbnq = torch.empty((N, 1, H, W), dtype=torch.float32, device=x.device)
+    bnb = FUSE_ATTN_BN_REDUCE and K.query("vu_attn_psi_bwd_bnb_ok", F)
+    tail = bool(bnb) and _attn_tail_ok(M, P, F, g, x, dout, dg_out, w1x1_dgrad(wg.weight, M.d),
+                                       w1x1_dgrad(wx.weight, M.d), dx)
+    # (fused tail: dx = dout * psi is formed there, not stored here)
     K.call("vu_attn_gate_bwd", K.ptr(dout), K.pstride(dout), K.ptr(x), K.pstride(x), K.ptr(pmap),
-           P, x.shape[1], K.ptr(dx), K.pstride(dx), K.ptr(dbnq), M.d, K.stream())
+           P, x.shape[1], None if tail else K.ptr(dx), K.pstride(dx), K.ptr(dbnq), M.d, K.stream())
     # BatchNorm2d(1) backward (fp32 single channel)
     gw, accw = grad_sink(bnp.weight)
     gb, _ = grad_sink(bnp.bias)
     dq = torch.empty_like(q)
     K.bn_backward(dbnq, q, cq, bnp.weight, False, gw, gb, accw, dq, F32, train=bnp.training)
     # psi conv + ReLU backward -> ds (grad of g1 + x1)
-    ds = M.act(N, F, H, W)
+    ds = None if tail else M.act(N, F, H, W)
     gwp, accp = grad_sink(wp.weight)
     gbp, _ = grad_sink(wp.bias)
     ws = K.workspace_f32(K.query("vu_attn_psi_bwd_workspace_bytes", P, F), x.device)
     pg = px = None
-    if FUSE_ATTN_BN_REDUCE and K.query("vu_attn_psi_bwd_bnb_ok", F):
+    if bnb:
         # the psi backward also emits both BatchNorms' first reduction stage
         # (round 6): no separate reduction passes over (ds, ug) and (ds, ux)
         nb = K.query("vu_attn_psi_bwd_blocks", P)
         bg = torch.empty((nb, 2, F), dtype=torch.float32, device=x.device)
         bx = torch.empty_like(bg)
         K.call("vu_attn_psi_bwd_bnb", K.ptr(ug), K.ptr(ux), P, F, K.ptr(cg[0]), K.ptr(cg[1]),
-               K.ptr(cx[0]), K.ptr(cx[1]), K.ptr(wp.weight), K.ptr(dq), K.ptr(ds), K.ptr(gwp),
-               K.ptr(gbp), 1 if accp else 0, K.ptr(ws), K.ptr(cg[2]), K.ptr(cg[3]), K.ptr(cx[2]),
+               K.ptr(cx[0]), K.ptr(cx[1]), K.ptr(wp.weight), K.ptr(dq), None if tail else K.ptr(ds),
+               K.ptr(gwp), K.ptr(gbp), 1 if accp else 0, K.ptr(ws), K.ptr(cg[2]), K.ptr(cg[3]), K.ptr(cx[2]),
                K.ptr(cx[3]), K.ptr(bg), K.ptr(bx), M.d, K.stream())
         pg, px = K.BnbPart(bg, nb, ug), K.BnbPart(bx, nb, ux)
     else:
         K.call("vu_attn_psi_bwd", K.ptr(ug), K.ptr(ux), P, F, K.ptr(cg[0]), K.ptr(cg[1]),
                K.ptr(cx[0]), K.ptr(cx[1]), K.ptr(wp.weight), K.ptr(dq), K.ptr(ds), K.ptr(gwp),
                K.ptr(gbp), 1 if accp else 0, K.ptr(ws), M.d, K.stream())
-    if pg is not None:
+    if tail:
+        # both fp64 finishes (bn_bwd_pair's), then the one pass
+        ks = []
+        for u_, c_, bn_, part in ((ug, cg, bng, pg), (ux, cx, bnx, px)):
+            gw_, gb_, acc_ = bn_grad_sinks(bn_)
+            ks.append(K.bn_backward_finish(part, u_, c_, bn_.weight, gw_, gb_, acc_, train=bn_.training))
+        dug, dux = torch.empty_like(ug), torch.empty_like(ux)
+        wdg, wdx = w1x1_dgrad(wg.weight, M.d), w1x1_dgrad(wx.weight, M.d)
+        dst, coff = dg_out
+
+        def run_tail():
+            K.call("vu_attn_tail_bwd", K.ptr(ug), K.ptr(ux), K.ptr(dq), P, F, x.shape[1], K.ptr(cg[0]),
+                   K.ptr(cg[1]), K.ptr(cx[0]), K.ptr(cx[1]), K.ptr(wp.weight), K.ptr(cg[2]), K.ptr(ks[0]),
+                   K.ptr(cx[2]), K.ptr(ks[1]), K.ptr(wdg), wdg.shape[-1], K.ptr(wdx), wdx.shape[-1],
+                   K.ptr(dout), K.pstride(dout), K.ptr(pmap), K.ptr(dst), K.pstride(dst), coff,
+                   1 if dg_acc else 0, K.ptr(dx), K.pstride(dx), K.ptr(dug), K.ptr(dux), M.d, K.stream())
+        if K.AUDIT is None:
+            run_tail()
+        else:
+            # a GEMM audit sees the two input-gradient GEMMs inside the one
+            # launch: dg (+)= dug W_g, and dx = (dout * psi) + dux W_x with the
+            # accumulate operand -- what the gate backward would have stored
+            # -- put into dx beforehand
+            dx.copy_(dout.float() * pmap)
+            K.audited_gemm(K.gather1x1([dug]), wdg, g.shape[1], dst, M.d, coff, dg_acc,
+                           lambda: K.audited_gemm(K.gather1x1([dux]), wdx, x.shape[1], dx, M.d, 0, True, run_tail))
+    elif pg is not None:
         dug, dux = bn_bwd_pair(ds, (ug, cg, bng, pg), (ux, cx, bnx, px), M)
     else:
         dug = bn_bwd(ds, ug, cg, bng, False, M)
@@ -773,6 +824,8 @@ def attention_bwd(M, att, saved, dout, dg_out, dg_acc):
         M.notify([wg.weight, wg.bias, wx.weight, wx.bias, wp.weight, wp.bias, bng.weight, bng.bias,
                   bnx.weight, bnx.bias, bnp.weight, bnp.bias])
     M.side(wgs, dug, dux, g, x)
+    if tail:
+        return dx
     # input gradients of the two 1x1 convs
     if dg_out is not None:
         dst, coff = dg_out

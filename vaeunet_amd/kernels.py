@@ -182,6 +182,28 @@ class BnbPart:
         self.part, self.nblk, self.x = part, nblk, x
 
 
+def audited_gemm(g, wmat, ncol, out, dtype, out_coff, accumulate, launch):
+    """Run ``launch`` -- a fused kernel that contains the plain GEMM
+    out[:, out_coff:out_coff+ncol] (=|+=) A wmat^T among its work -- so that an
+    installed AUDIT checks that GEMM per element like a vu_gemm_fwd launch of
+    the same descriptor (A may be written by the launch itself: the audit
+    reads the operands after it).  The record names the kernel that would
+    serve the descriptor alone."""
+    if AUDIT is None:
+        return launch()
+    a = VuGemmFwd()
+    a.a = g
+    a.b = wmat.data_ptr()
+    a.ldb = wmat.shape[-1] if wmat.dim() == 2 else wmat.stride(0)
+    a.ncol = ncol
+    a.out = out.data_ptr()
+    a.out_stride = pstride(out)
+    a.out_coff = out_coff
+    a.out_mode = 0
+    a.accumulate = 1 if accumulate else 0
+    return AUDIT.gemm_fwd(a, dtype, g, wmat, out, None, None, launch)
+
+
 def gemm_fwd(g, wmat, ncol, out, dtype, out_coff=0, bias=None, stats=False, accumulate=False,
              convT=None, kind="fwd", strided=None, bnb=None, flops=None, relu=False, zbias=None):
     """out[m][j] = sum_k A[m][k] wmat[j][k] (+bias).  convT=(oH,oW,opy,opx,cout) selects
