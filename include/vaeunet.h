@@ -693,6 +693,65 @@ int vu_seg_metrics(const int64_t* counts, int P, int C, double eps, float* out,
                    float* pooled, int pooled_accumulate, int64_t* class_total,
                    void* stream);
 
+/* ---- calibration and uncertainty metrics (utils/uncertainty_metrics.py) -- */
+/* Unpinned vs the reference (its utils/uncertainty_metrics.py was not
+ * available): the definitions below are this project's.
+ *
+ * vu_calib_hist: one streaming pass over n probabilities p (fp32, dense), the
+ * mask (mdtype 0 = fp32, 1 = uint8 / bool, 2 = int64; truth = (float)mask >
+ * 0.5f) and, optionally, an uncertainty map u (fp32, dense; NULL together
+ * with unc_hist when absent).  Any base alignment (a misaligned head and the
+ * tail are read element-wise).  Per pixel with a non-NaN p, pc = min(max(p,
+ * 0), 1), R = VU_CALIB_RANK_BINS:
+ *   conf_hist[nb][2]  bin min((int)(pc * (float)nb), nb-1), column truth
+ *   conf_sum[nb]      sum of (double)pc per confidence bin
+ *   rank_hist[R][2]   bin min((int)(pc * (float)R), R-1), column truth
+ *   unc_hist[R][2]    bin min((int)(max(u, 0) * uscale), R-1), column
+ *                     (pc > 0.5f) != truth; pixels with a NaN u are left out
+ *   sums[2]           {sum d*d with d = (double)pc - t,  sum -[t log q +
+ *                     (1-t) log(1-q)] with q = (double)pc clamped to [1e-7,
+ *                     1 - 1e-7], fp64 log}
+ *   invalid[2]        {pixels with NaN p (left out of everything), pixels with
+ *                     a valid p and a NaN u (left out of unc_hist only)}
+ * Each bin index is one fp32 multiply and one truncation; uscale = R / u_max
+ * rounded once to fp32 by the caller.  The integer outputs are exact and do
+ * not depend on the grid or the order; the fp64 outputs are summed in a fixed
+ * order (per-lane, per-block, then over the blocks of the workspace) and are
+ * bit-identical from run to run.  accumulate != 0 adds into all six outputs
+ * instead of storing.  Limits: 1 <= n < 2^31 per call, 1 <= nb <= 64.
+ * workspace: vu_calib_workspace_bytes bytes. */
+#define VU_CALIB_RANK_BINS 1024
+#define VU_CALIB_NSCALARS 12
+int64_t vu_calib_workspace_bytes(void);
+int vu_calib_hist(const float* p, const void* mask, int mdtype, const float* u,
+                  int64_t n, int nb, float uscale, int64_t* conf_hist,
+                  double* conf_sum, int64_t* rank_hist, int64_t* unc_hist,
+                  double* sums, int64_t* invalid, int accumulate,
+                  void* workspace, void* stream);
+/* The totals of vu_calib_hist -> metrics, fp64 throughout, one launch.  N =
+ * valid pixels, P = positives, Q = negatives (from rank_hist).
+ *   reliability[nb][3] = {count_b, acc_b = pos_b / count_b, conf_b =
+ *     conf_sum_b / count_b} (0, 0 for an empty bin)
+ *   scalars[VU_CALIB_NSCALARS] = {ece = sum_b count_b/N |acc_b - conf_b|,
+ *     mce = max_b |acc_b - conf_b| over non-empty bins, brier = sums[0]/N,
+ *     nll = sums[1]/N, auroc, auroc_tie_bound, auprc, ause, N, P, N_u, E}
+ *   auroc = (sum_b pos_b * (neg in bins < b) + 0.5 sum_b pos_b neg_b) / (P Q)
+ *     (a rank bin is a tie group; NaN when P Q == 0); auroc_tie_bound =
+ *     sum_b pos_b neg_b / (2 P Q) bounds |auroc - exact AUROC|
+ *   auprc = average precision over the rank bins in descending score, one
+ *     threshold per non-empty bin: sum_k (recall_k - recall_{k-1}) *
+ *     precision_k (NaN when P == 0)
+ *   sparsification[R+1][3]: row k removes the k highest-uncertainty bins (C_k
+ *     pixels, Ecum_k of the E errors among the N_u pixels of unc_hist):
+ *     {frac_k = C_k / N_u, err_k = (E - Ecum_k) / (N_u - C_k), oracle_k =
+ *     max(E - C_k, 0) / (N_u - C_k)} (err, oracle = 0 when N_u == C_k); ause =
+ *     trapezoid over frac of err - oracle.  unc_hist == NULL: the table,
+ *     ause, N_u and E are NaN. */
+int vu_calib_metrics(const int64_t* conf_hist, const double* conf_sum, int nb,
+                     const int64_t* rank_hist, const int64_t* unc_hist,
+                     const double* sums, double* scalars, double* reliability,
+                     double* sparsification, void* stream);
+
 /* ---- optimizer (train.py:334,406-411) ---------------------------------- */
 /* sum of squares of n fp32 values into out (fp64, deterministic) */
 int vu_sumsq(const float* x, int64_t n, double* out, double* workspace,

@@ -4,6 +4,8 @@ Drop-in surface (same names / signatures / state_dict keys as the reference):
   unet.UNet, unet.unet_parts.{DoubleConv, Down, Up, AttentionGate, OutConv},
   unet.unet_resnet.{UNetResNet, DecoderBlock}, utils.loss.*, utils.metrics.{dice_score,
   iou_score, precision_recall, specificity, accuracy, get_all_metrics}, evaluate.evaluate
+Calibration / uncertainty metrics (utils/uncertainty_metrics.py's numbers; unpinned):
+  calibration.{calib_hist, calib_metrics, CalibrationMeter}
 Dispatcher ops: torch.ops.vaeunet.* (vaeunet_amd.ops)
 """
 from .unet_model import UNet  # noqa: F401
@@ -13,3 +15,4 @@ from . import ops  # noqa: F401,E402  (registers torch.ops.vaeunet.*)
 from .metrics import (dice_score, iou_score, precision_recall, specificity, accuracy,  # noqa: F401,E402
                       get_all_metrics, seg_counts, seg_metrics, SegmentationMeter)
 from .evaluate import evaluate  # noqa: F401,E402
+from .calibration import calib_hist, calib_metrics, CalibrationMeter, CalibCounts  # noqa: F401,E402

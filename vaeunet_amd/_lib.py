@@ -183,6 +183,9 @@ _SIGS = {
     "vu_seg_counts": (_i, [_p, _i, C.POINTER(_l), _i, _i, _p, _i, C.POINTER(_l), _i, _i, _i, _i, _i, _i, _p, _i, _p,
                            _p, _p]),
     "vu_seg_metrics": (_i, [_p, _i, _i, C.c_double, _p, _p, _i, _p, _p]),
+    "vu_calib_workspace_bytes": (_l, []),
+    "vu_calib_hist": (_i, [_p, _p, _i, _p, _l, _i, _f, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
+    "vu_calib_metrics": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
     "vu_mt_chunk_elems": (_l, []),
     "vu_mt_grad_norm": (_i, [_p, _i, _l, _f, _p, _p, _p, _p]),
     "vu_mt_scale_grads": (_i, [_p, _i, _l, _p, _p]),

@@ -29,14 +29,18 @@ Reference ops each one replaces:
   bce_dice_loss                  CombinedLoss.forward             utils/loss.py:45-63
   seg_counts                     F.interpolate + (x > 0.5) + the TP/FP/FN/TN sums of evaluate.py /
                                  utils/metrics.py get_all_metrics (integer output, not differentiable)
+  calib_hist                     the histogram / sum passes of utils/uncertainty_metrics.py (ECE, Brier,
+                                 NLL, AUROC / AUPRC, sparsification) as one fused pass
 """
 import ctypes as C
 import types
+from typing import List, Optional
 import torch
 
 from . import _lib
 from . import engine as E
 from . import kernels as K
+from . import calibration as _calibration
 from . import metrics as _metrics
 from ._lib import call, ptr, query, stream
 from .engine import conv_layout, convT_layout, w3x3_dgrad, w3x3_fwd, wT_dgrad, wT_fwd
@@ -640,7 +644,35 @@ def _(logits, masks, align_corners=False):
     return torch.empty((logits.shape[0], logits.shape[1], 4), dtype=torch.int64, device=logits.device)
 
 
+# ---- calibration histograms ----------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::calib_hist", mutates_args=(), device_types="cuda")
+def calib_hist(prob: torch.Tensor, target: torch.Tensor, uncertainty: Optional[torch.Tensor] = None,
+               n_bins: int = 15, u_max: float = 0.6931471805599453) -> List[torch.Tensor]:
+    """The totals of vaeunet_amd.calibration.calib_hist as tensors: conf_hist
+    int64 [n_bins, 2], conf_sum fp64 [n_bins], rank_hist int64 [1024, 2],
+    unc_hist int64 [1024, 2] ([0, 2] without an uncertainty map), sums fp64 [2],
+    invalid int64 [2].  Not differentiable (integer / accumulated outputs)."""
+    c = _calibration.calib_hist(prob, target, uncertainty, n_bins=n_bins, u_max=u_max)
+    unc = c.unc_hist if c.unc_hist is not None else torch.empty((0, 2), dtype=torch.int64, device=prob.device)
+    return [c.conf_hist, c.conf_sum, c.rank_hist, unc, c.sums, c.invalid]
+
+
+@calib_hist.register_fake
+def _(prob, target, uncertainty=None, n_bins=15, u_max=0.6931471805599453):
+    if prob.shape != target.shape or (uncertainty is not None and uncertainty.shape != prob.shape):
+        raise ValueError(f"vaeunet::calib_hist: prob {tuple(prob.shape)}, target {tuple(target.shape)} and the "
+                         "uncertainty map must share one shape")
+    if not 1 <= n_bins <= _calibration.MAX_CONF_BINS:
+        raise ValueError(f"vaeunet::calib_hist: n_bins must be in [1, {_calibration.MAX_CONF_BINS}], got {n_bins}")
+    R = _calibration.RANK_BINS
+    i64 = dict(dtype=torch.int64, device=prob.device)
+    f64 = dict(dtype=torch.float64, device=prob.device)
+    return [torch.empty((n_bins, 2), **i64), torch.empty(n_bins, **f64), torch.empty((R, 2), **i64),
+            torch.empty((R if uncertainty is not None else 0, 2), **i64), torch.empty(2, **f64),
+            torch.empty(2, **i64)]
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
-       "bce_dice_loss", "seg_counts")
+       "bce_dice_loss", "seg_counts", "calib_hist")
