@@ -913,6 +913,16 @@ def test_upsample_bilinear(mode, case):
     dx = K.empty_act(N, C_, hi, wi, _dt(mode), DEV)
     K.upsample_bwd(_act(dy, mode), dx, ho, wo, py, px, False, d)
     _close(dx, xr.grad, mode, what="upsample bwd")
+    # accumulate onto a random pre-fill: the same tolerance plus the storage
+    # rounding of the pre-fill's magnitude
+    base = torch.randn(N, C_, hi, wi, generator=g).to(_dt(mode)).float()
+    dxa = _act(base, mode)
+    K.upsample_bwd(_act(dy, mode), dxa, ho, wo, py, px, True, d)
+    want = xr.grad + base
+    rtol = 2e-5 if mode == "f32" else 1.5e-2
+    bound = rtol * max(xr.grad.abs().max().item(), 1e-3) + U_STORE[mode] * base.abs()
+    err = (dxa.float().cpu() - want).abs()
+    assert (err <= bound).all(), f"upsample bwd accumulate: max err {float(err.max()):.3e}"
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16"])
@@ -1183,3 +1193,85 @@ def test_outconv_pointwise_fwd(shape, d):
         mag = F.conv2d(x.float().abs(), conv.weight.abs()) + conv.bias.abs()[None, :, None, None]
     assert y.shape == ref.shape
     assert ((y - ref).abs() <= 1e-5 * mag + 1e-6).all(), float((y - ref).abs().max())
+
+
+# ----------------------------------------------------------------------------
+# small movers of resample.hip: vu_copy, vu_zero, vu_zero_insert2
+# ----------------------------------------------------------------------------
+def _layout(C, layout):
+    """(wide, c0) of a channel slice: dense; the upper half of a tensor twice
+    as wide (pixel stride a multiple of 8 when C is); a slice at a pixel
+    stride that is no multiple of 8 (the scalar path whatever C)."""
+    return {"dense": (None, 0), "slice": (2 * C, C), "odd": (2 * C + 4, 4)}[layout]
+
+
+@pytest.mark.parametrize("acc", [False, True])
+@pytest.mark.parametrize("layout", ["dense", "slice", "odd"])
+@pytest.mark.parametrize("C", [3, 8, 24])
+@pytest.mark.parametrize("pair", [("f32", "f32"), ("f32", "bf16"), ("bf16", "f32"), ("bf16", "bf16")],
+                         ids=lambda p: f"{p[0]}-{p[1]}")
+def test_copy_cast_accumulate(pair, C, layout, acc):
+    """vu_copy (K.copy): y = cast(x) or y = cast(fp32(y) + fp32(x)), bit for
+    bit, on the 8-wide path (same dtype, C % 8 == 0, strides % 8 == 0) and the
+    casting / scalar path; the neighbouring channels stay untouched."""
+    import ref_small as R
+    K, _ = _k()
+    mi, mo = pair
+    N, H, W = 2, 3, 5
+    g = torch.Generator().manual_seed(31)
+    x = torch.randn(N, C, H, W, generator=g).to(_dt(mi))
+    y0 = torch.randn(N, C, H, W, generator=g).to(_dt(mo))
+    wide, c0 = _layout(C, layout)
+    xd, gx = R.guarded_act(N, C, H, W, _dt(mi), DEV, wide=wide, c0=c0)
+    yd, gy = R.guarded_act(N, C, H, W, _dt(mo), DEV, wide=wide, c0=c0)
+    xd.copy_(x)
+    yd.copy_(y0)
+    K.copy(xd, yd, acc)
+    torch.cuda.synchronize()
+    gx.check("copy x")
+    gy.check("copy y")
+    assert torch.equal(xd.cpu(), x)
+    want = (y0.float() + x.float()).to(_dt(mo)) if acc else x.to(_dt(mo))
+    assert torch.equal(yd.cpu(), want)
+
+
+@pytest.mark.parametrize("mode,C", [("bf16", 2), ("bf16", 8), ("bf16", 40), ("f32", 8), ("f32", 40)])
+def test_zero_channel_slice(mode, C):
+    """vu_zero (K.zero) on the middle channel slice of a tensor three times as
+    wide (C * elem, the pixel stride in bytes and the base pointer multiples
+    of 4): the slice is zero, its neighbours bit-unchanged."""
+    import ref_small as R
+    K, _ = _k()
+    N, H, W = 2, 3, 5
+    y, gy = R.guarded_act(N, C, H, W, _dt(mode), DEV, wide=3 * C, c0=C)
+    assert y.data_ptr() % 4 == 0 and (3 * C * y.element_size()) % 4 == 0
+    K.zero(y)
+    torch.cuda.synchronize()
+    gy.check("zero")
+    assert y.shape == (N, C, H, W) and not y.any()
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+@pytest.mark.parametrize("C", [8, 64])
+@pytest.mark.parametrize("ew", [1, 0], ids=["W=2w-1", "W=2w"])
+@pytest.mark.parametrize("eh", [1, 0], ids=["H=2h-1", "H=2h"])
+@pytest.mark.parametrize("hw", [(1, 1), (1, 5), (5, 1), (5, 5)])
+def test_zero_insert2(hw, eh, ew, C, mode):
+    """vu_zero_insert2: up[2i, 2j] = dy[i, j], zero elsewhere, for both
+    parities of the output size and a strided dy."""
+    import ref_small as R
+    from vaeunet_amd import _lib
+    h, w = hw
+    N, H, W = 2, 2 * h - eh, 2 * w - ew
+    g = torch.Generator().manual_seed(32)
+    dy = torch.randn(N, C, h, w, generator=g).to(_dt(mode))
+    dyd, gd = R.guarded_act(N, C, h, w, _dt(mode), DEV, wide=2 * C, c0=C)
+    dyd.copy_(dy)
+    up, gu = R.guarded_act(N, C, H, W, _dt(mode), DEV)
+    _lib.call("vu_zero_insert2", _lib.ptr(dyd), 2 * C, N, h, w, C, _lib.ptr(up), C, H, W, _code(mode), _lib.stream())
+    torch.cuda.synchronize()
+    gd.check("zero_insert2 dy")
+    gu.check("zero_insert2 up")
+    ref = torch.zeros(N, C, H, W, dtype=_dt(mode))
+    ref[:, :, 0:2 * h:2, 0:2 * w:2] = dy
+    assert torch.equal(up.cpu(), ref)

@@ -117,3 +117,162 @@ def test_fused_optimizer_training_loop_matches_torch():
     for a, b in zip(losses["torch"][1:], losses["fused"][1:]):
         assert abs(a - b) < 2e-4 * max(1.0, abs(a)), losses
     assert losses["fused"][3] != losses["fused"][0]
+
+
+# ----------------------------------------------------------------------------
+# capturable AdamW (vu_mt_adamw_dev / vu_mt_adamw_dev_scaled), kernel level
+# ----------------------------------------------------------------------------
+LR, WD, B1, B2, EPS = 1e-3, 1e-2, 0.9, 0.999, 1e-8   # (1 - LR * WD != 1 in fp32: the decay is exercised)
+# (numel, param/moment offset, grad offset) in floats past a 16-byte boundary:
+# around the 8192-element chunk (tail, exact, one over, several chunks); an
+# offset of 1 misaligns the views, which selects the kernel's scalar path
+MT_TENSORS = [(1, 0, 0), (3, 0, 0), (8191, 0, 0), (8192, 0, 0), (8193, 0, 0), (9001, 0, 0), (2 * 8192 + 5, 0, 0),
+              (3, 1, 1), (8193, 1, 1), (9001, 1, 1), (2 * 8192 + 5, 0, 1)]
+
+
+def _mt_values(seed=31):
+    g = torch.Generator().manual_seed(seed)
+    return [dict(p=torch.randn(n, generator=g), m=torch.randn(n, generator=g) * 0.1,
+                 v=torch.rand(n, generator=g) * 0.01 + 1e-3) for n, _, _ in MT_TENSORS]
+
+
+def _mt_grads(seed):
+    g = torch.Generator().manual_seed(seed)
+    return [torch.randn(n, generator=g) * 0.3 for n, _, _ in MT_TENSORS]
+
+
+class _MtSet:
+    """One replica of the tensor set on the device, every tensor in a guarded
+    buffer at its (mis)alignment."""
+
+    def __init__(self, values):
+        import ref_small as R
+        self.t, self.guards = [], []
+        for val, (n, off, goff) in zip(values, MT_TENSORS):
+            row = {}
+            for key, o in (("p", off), ("g", goff), ("m", off), ("v", off)):
+                row[key], gd = R.guarded(n, torch.float32, DEV, offset=o)
+                assert row[key].data_ptr() % 16 == (4 * o) % 16
+                if key != "g":
+                    row[key].copy_(val[key])
+                self.guards.append(gd)
+            self.t.append(row)
+        self.step, gs = R.guarded(1, torch.float32, DEV)
+        self.step.zero_()
+        self.guards.append(gs)
+
+    def set_grads(self, grads):
+        for row, g in zip(self.t, grads):
+            row["g"].copy_(g)
+
+    def table(self, step_size=0.0, bc2s=1.0):
+        from vaeunet_amd.optim import _Table
+        return _Table([(r["p"], r["g"], r["m"], r["v"], step_size, bc2s) for r in self.t], DEV)
+
+    def check(self, what):
+        torch.cuda.synchronize()
+        for gd in self.guards:
+            gd.check(what)
+
+    def same_bits(self, other, what, keys=("p", "m", "v")):
+        for i, (a, b) in enumerate(zip(self.t, other.t)):
+            for k in keys:
+                assert torch.equal(a[k], b[k]), (
+                    f"{what}: tensor {i} {MT_TENSORS[i]} '{k}' differs in "
+                    f"{int((a[k] != b[k]).sum())} elements, max {float((a[k] - b[k]).abs().max()):.3e}")
+
+
+def _dev_step(s, zero_grad, scale=None, scaled_entry=False):
+    from vaeunet_amd import _lib
+    tab = s.table()
+    if scaled_entry:
+        _lib.call("vu_mt_adamw_dev_scaled", tab.ptr(), tab.n, tab.nchunks, LR, WD, B1, B2, EPS, _lib.ptr(s.step),
+                  zero_grad, _lib.ptr(scale), _lib.stream())
+    else:
+        _lib.call("vu_mt_adamw_dev", tab.ptr(), tab.n, tab.nchunks, LR, WD, B1, B2, EPS, _lib.ptr(s.step),
+                  zero_grad, _lib.stream())
+    torch.cuda.synchronize()
+
+
+def test_capturable_adamw_same_bits_as_host_path():
+    """Three steps of vu_mt_adamw_dev (device step counter, zero_grad = 0) give
+    p / m / v bit-identical to three vu_mt_adamw launches with step_size and
+    bc2_sqrt computed on the host as FusedAdamW.step does -- "the same values
+    as the host path" -- on the 16-byte and the scalar path and across chunk
+    tails; and both are within the eager test's tolerances of an fp64 AdamW on
+    the CPU (the independent reference: the identity alone would not catch a
+    shared mistake)."""
+    import ref_small as R
+    from vaeunet_amd import _lib
+    vals = _mt_values()
+    host, dev = _MtSet(vals), _MtSet(vals)
+    ref = [(v["p"].double(), v["m"].double(), v["v"].double()) for v in vals]
+    for step in (1, 2, 3):
+        grads = _mt_grads(40 + step)
+        host.set_grads(grads)
+        dev.set_grads(grads)
+        bc1, bc2 = 1 - B1 ** float(step), 1 - B2 ** float(step)
+        tab = host.table(LR / bc1, bc2 ** 0.5)
+        _lib.call("vu_mt_adamw", tab.ptr(), tab.n, tab.nchunks, 1.0 - LR * WD, 1.0 - B1, float(B2), 1.0 - B2,
+                  float(EPS), None, _lib.stream())
+        _dev_step(dev, 0)
+        host.check(f"host step {step}")
+        dev.check(f"dev step {step}")
+        assert float(dev.step) == float(step)
+        dev.same_bits(host, f"step {step}")
+        for row, g in zip(dev.t, grads):
+            assert torch.equal(row["g"].cpu(), g), "zero_grad = 0 changed a gradient"
+        ref = [R.adamw_ref(p, m, v, g, step, LR, WD, B1, B2, EPS) for (p, m, v), g in zip(ref, grads)]
+    for row, (p, m, v) in zip(dev.t, ref):
+        torch.testing.assert_close(row["p"].double().cpu(), p, rtol=1e-6, atol=1e-9)
+        torch.testing.assert_close(row["m"].double().cpu(), m, rtol=1e-6, atol=1e-6 * float(m.abs().max()))
+        torch.testing.assert_close(row["v"].double().cpu(), v, rtol=1e-6, atol=1e-6 * float(v.abs().max()))
+
+
+@pytest.mark.parametrize("coef", [0.37, 1.0, None], ids=["clip", "one", "null"])
+def test_capturable_adamw_fused_clip_scale_same_bits(coef):
+    """vu_mt_scale_grads(c) then vu_mt_adamw_dev(zero_grad = 1) equals
+    vu_mt_adamw_dev_scaled(zero_grad = 1, grad_scale = c) bit for bit (c a
+    clip coefficient below 1, c = 1, and grad_scale = NULL against the
+    unscaled step); gradients are exactly zero afterwards, the step counter
+    has advanced by one, guard regions are untouched."""
+    from vaeunet_amd import _lib
+    vals = _mt_values()
+    two, one = _MtSet(vals), _MtSet(vals)
+    grads = _mt_grads(50)
+    two.set_grads(grads)
+    one.set_grads(grads)
+    c = None if coef is None else torch.tensor([coef], dtype=torch.float32, device=DEV)
+    if c is not None:
+        tab = two.table()
+        _lib.call("vu_mt_scale_grads", tab.ptr(), tab.n, tab.nchunks, _lib.ptr(c), _lib.stream())
+        torch.cuda.synchronize()
+        for row, g in zip(two.t, grads):
+            assert torch.equal(row["g"].cpu(), g * torch.tensor(coef, dtype=torch.float32))
+    _dev_step(two, 1)
+    _dev_step(one, 1, scale=c, scaled_entry=True)
+    two.check("scale + step")
+    one.check("fused scale step")
+    one.same_bits(two, f"grad_scale {coef}")
+    for s in (one, two):
+        assert float(s.step) == 1.0
+        for row in s.t:
+            assert not row["g"].any(), "gradient not cleared"
+    # and the step moved the parameters at all
+    assert all(not torch.equal(r["p"].cpu(), v["p"]) for r, v in zip(one.t, vals))
+
+
+def test_capturable_adamw_scaled_refuses_keeping_grads():
+    """grad_scale with zero_grad = 0 is refused (the scaled gradient is never
+    stored), and nothing is touched."""
+    vals = _mt_values()
+    s = _MtSet(vals)
+    grads = _mt_grads(60)
+    s.set_grads(grads)
+    c = torch.tensor([0.5], dtype=torch.float32, device=DEV)
+    with pytest.raises(RuntimeError):
+        _dev_step(s, 0, scale=c, scaled_entry=True)
+    s.check("refused")
+    assert float(s.step) == 0.0
+    for row, v, g in zip(s.t, vals, grads):
+        assert torch.equal(row["p"].cpu(), v["p"]) and torch.equal(row["g"].cpu(), g)
