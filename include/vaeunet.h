@@ -463,6 +463,27 @@ int vu_bn_bwd_apply2(const void* dy, int64_t dys, const void* x1, int64_t x1s, c
                      int64_t P, int C, const float* mean1, const float* coef1, const float* mean2,
                      const float* coef2, void* dx1, int64_t dx1s, void* dx2, int64_t dx2s, int dtype,
                      void* stream);
+/* Weight gradient of the 3-channel image convolution (inc.0) with the
+ * BatchNorm(+ReLU) backward apply of its output gradient formed in the
+ * operand path, bf16 (csrc/conv_image_wgrad.hip):
+ *   slab[s][co][tap*8 + ci] = sum_{pixels p of block s} dy[p][co] * img[p + tap][ci]
+ *   dy = the bytes vu_bn_bwd_apply(da, y; scale, shift, mean, k, relu) would store
+ * (never written).  da, y: NHWC, 64 channels, pixel strides das, ys; img: the
+ * 8-channel packed image (vu_input_pack), pixel stride imgs, 3x3 / stride 1 /
+ * pad 1 taps; k: the [3][64] coefficients of vu_bn_bwd_reduce /
+ * vu_bn_bwd_finish.  slab: nslab fp32 slabs [64][72] (one per block, any
+ * nslab >= 1; vu_conv_image_wgrad_bn_slabs: the count the kernel is sized for),
+ * summed by vu_slab_reduce(slab, nslab, 64, 72, 8, cvalid, ...) in a fixed
+ * order.  y = NULL: da IS dy (the plain weight gradient; coefficients unused).
+ * _ok: bf16, C == 64, Cp == 8 packed channels, strides % 8 == 0 and >= the
+ * channel count, N*H*W < 2^31. */
+int vu_conv_image_wgrad_bn_ok(int C, int Cp, int64_t das, int64_t ys, int64_t imgs, int N, int H, int W,
+                              int dtype);
+int vu_conv_image_wgrad_bn_slabs(int N, int H, int W);
+int vu_conv_image_wgrad_bn(const void* da, int64_t das, const void* y, int64_t ys, const float* scale,
+                           const float* shift, const float* mean, const float* k, int relu,
+                           const void* img, int64_t imgs, int N, int H, int W, float* slab, int nslab,
+                           void* stream);
 
 /* ---- per-channel reductions / elementwise ------------------------------ */
 /* out[c] (=|+=) sum over the pixels of the (Hr, Wr) window at (y0, x0) of

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "host.h"
+#include "bn_bwd_elem.h"
 
 namespace {
 
@@ -425,11 +426,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* dy, int64_t 
       if (p >= P) continue;
       Vec8<T> vo;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        float xv = vx[u].get(i), dz = vd[u].get(i);
-        if (relu && !(fmaf(xv, sc[i], sf[i]) > 0.f)) dz = 0.f;
-        vo.set(i, fmaf(k1[i], dz, k2[i] * (xv - mu[i])) + k3[i]);
-      }
+      for (int i = 0; i < 8; ++i)
+        vo.set(i, bn_bwd_elem(vx[u].get(i), vd[u].get(i), relu, sc[i], sf[i], mu[i], k1[i], k2[i], k3[i]));
       vo.store(dx + p * dxs + c);
     }
   }

@@ -575,6 +575,54 @@ def conv_bn_relu_fwd(M, srcs, conv, bn, cin_pad=None, defer=False, zbias=None, c
     return a, (y, coef)
 
 
+# The first convolution of the network (inc.double_conv[0]) needs no input
+# gradient, so its weight gradient is the only reader of dy = the BN1 backward
+# apply's output: the apply then runs in that weight gradient's operand path
+# (vu_conv_image_wgrad_bn) and dy is never stored.  dgamma, dbeta and the
+# apply coefficients come from the same reduce / finish launches as before.
+# Where dy is stored anyway (the caller wants the image's gradient, or a small
+# tensor takes vu_bn_bwd_fused) the same kernel runs over it without the
+# transform.  Module-level switch for A/B runs (bench.py --engine-flag): off,
+# the image weight gradient is vu_gemm_wgrad's as before.
+FUSE_IMAGE_WGRAD_BN = True
+
+
+def _image_wgrad_kernel_serves(M, srcs, conv, shortcut, da, y):
+    """conv_image_wgrad.hip runs this weight gradient (da, y: the BatchNorm's
+    output gradient and input, or the stored dy twice)."""
+    if not FUSE_IMAGE_WGRAD_BN or shortcut is not None or M.d != BF16 or K.AUDIT is not None:
+        return False
+    if len(srcs) != 1 or not conv.weight.requires_grad:
+        return False
+    return K.image_wgrad_bn_ok(da, y, srcs[0], M.d)
+
+
+def _image_wgrad_bn_serves(M, srcs, conv, bn, y, da, need_dsrc, da_part, shortcut):
+    if need_dsrc or isinstance(da, PoolGrad) or (da_part is not None and da_part.x is not y):
+        return False
+    N, Cc, H, W = y.shape
+    # small tensors without epilogue partials take vu_bn_bwd_fused, which keeps
+    # its own reduction: they stay on it (dgamma / dbeta exactly as before)
+    if da_part is None and FUSED_BN_BWD and K.query("vu_bn_bwd_fused_supported", N * H * W, Cc, K.pstride(da),
+                                                    K.pstride(y), Cc):
+        return False
+    return _image_wgrad_kernel_serves(M, srcs, conv, shortcut, da, y)
+
+
+def _image_wgrad_bn(M, srcs, conv, bn, y, coef, da, cvalid, da_part):
+    gw, gb, acc = bn_grad_sinks(bn)
+    if da_part is not None:
+        k = K.bn_backward_finish(da_part, y, coef, bn.weight, gw, gb, acc, train=bn.training)
+    else:
+        k = K.bn_backward_reduce(da, y, coef, bn.weight, True, gw, gb, acc, M.d, train=bn.training)
+
+    def wg():
+        g, gacc = grad_sink(conv.weight)
+        K.image_wgrad_bn(da, y, coef, k, True, srcs[0], g, conv_layout(g), gacc, cvalid=cvalid)
+        M.notify([bn.weight, bn.bias, conv.weight])
+    M.side(wg, da, y, k, *srcs)
+
+
 def conv_bn_relu_bwd(M, srcs, conv, bn, saved, da, need_dsrc, cvalid=None, dsrc=None, dsrc_acc=False,
                      cin_pad=None, da_part=None, feeds=None, shortcut=None):
     """cin_pad: compute the input gradient for cin_pad channels (zero weight
@@ -591,13 +639,20 @@ def conv_bn_relu_bwd(M, srcs, conv, bn, saved, da, need_dsrc, cvalid=None, dsrc=
     GEMM's epilogue, returned as (dsrc, part) -- part None when the kernel
     cannot."""
     y, coef = saved
+    if _image_wgrad_bn_serves(M, srcs, conv, bn, y, da, need_dsrc, da_part, shortcut):
+        _image_wgrad_bn(M, srcs, conv, bn, y, coef, da, cvalid, da_part)
+        return None
     zrs = shortcut.regions(y) if shortcut is not None else None
     dy = bn_bwd(da, y, coef, bn, True, M, part=da_part, zrs=zrs)
     if shortcut is not None:
         shortcut.dy = dy
 
     def wg():
-        wgrad3x3(dy, srcs, conv.weight, M, cvalid, sink=shortcut.sink if shortcut is not None else None)
+        if _image_wgrad_kernel_serves(M, srcs, conv, shortcut, dy, dy):
+            g, gacc = grad_sink(conv.weight)
+            K.image_wgrad_bn(dy, None, None, None, False, srcs[0], g, conv_layout(g), gacc, cvalid=cvalid)
+        else:
+            wgrad3x3(dy, srcs, conv.weight, M, cvalid, sink=shortcut.sink if shortcut is not None else None)
         M.notify([bn.weight, bn.bias] + ([conv.weight] if shortcut is None else []))
     M.side(wg, dy, *srcs)
     if not need_dsrc:

@@ -643,6 +643,54 @@ def bn_backward_finish(part, x, coef, gamma, dgamma, dbeta, acc, train=True):
     return k
 
 
+def bn_backward_reduce(dy, x, coef, gamma, relu, dgamma, dbeta, acc, dtype, train=True):
+    """Only vu_bn_bwd_reduce (both stages): dgamma / dbeta written (or added)
+    and the apply coefficients k (3 x C) returned -- bn_backward's reduce +
+    apply path without its apply."""
+    N, Cc, H, W = x.shape
+    P = N * H * W
+    ws = torch.empty(query("vu_reduce_workspace_bytes", P, Cc) // 4 + 1, dtype=torch.float32, device=x.device)
+    k = torch.empty((3, Cc), dtype=torch.float32, device=x.device)
+    call("vu_bn_bwd_reduce", ptr(dy), pstride(dy), ptr(x), pstride(x), P, Cc, ptr(coef[0]),
+         ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), ptr(gamma), 1 if relu else 0,
+         1 if train else 0, ptr(dgamma), ptr(dbeta), 1 if acc else 0, ptr(k), ptr(ws), dtype,
+         stream())
+    return k
+
+
+def image_wgrad_bn_ok(da, y, img, dtype):
+    """vu_conv_image_wgrad_bn serves these layouts (bf16, 64 channels, the
+    8-channel packed image, 8-element-aligned pixel strides)."""
+    N, Cc, H, W = y.shape
+    return bool(query("vu_conv_image_wgrad_bn_ok", Cc, img.shape[1], pstride(da), pstride(y), pstride(img),
+                      N, H, W, dtype))
+
+
+def image_wgrad_bn(da, y, coef, k, relu, img, grad, layout, accumulate, cvalid=None, nslab=None):
+    """The image convolution's weight gradient with the BN(+ReLU) backward
+    apply of its output gradient in the operand path (vu_conv_image_wgrad_bn):
+    grad (=|+=) sum_p dy[p] x patch[p] with dy = vu_bn_bwd_apply(da, y; coef, k)
+    formed in registers, never stored.  y = None: da is dy itself.  The slabs
+    go through vu_slab_reduce like gemm_wgrad's (fixed order, cvalid, layout)."""
+    N, _, H, W = img.shape
+    if nslab is None:
+        nslab = query("vu_conv_image_wgrad_bn_slabs", N, H, W)
+    slab = torch.empty((nslab, 64, 72), dtype=torch.float32, device=grad.device)
+    none = y is None
+
+    def launch():
+        call("vu_conv_image_wgrad_bn", ptr(da), pstride(da), ptr(y), 0 if none else pstride(y),
+             None if none else ptr(coef[0]), None if none else ptr(coef[1]), None if none else ptr(coef[2]),
+             None if none else ptr(k), 1 if relu else 0, ptr(img), pstride(img), N, H, W, ptr(slab), nslab,
+             stream())
+    _timed("conv3x3_image_wgrad", 2 * N * H * W * 64 * 72, launch, "conv_image_wgrad_kernel",
+           lambda: f"{N}x{H}x{W} 64x72 slabs {nslab}" + ("" if none else " bn"))
+    s_i, s_tap, s_c = layout
+    call("vu_slab_reduce", ptr(slab), nslab, 64, 72, 8, 8 if cvalid is None else cvalid, s_i, s_tap, s_c,
+         ptr(grad), 1 if accumulate else 0, stream())
+    return slab
+
+
 def bn_backward_apply2(dy, x1, coef1, k1, dx1, x2, coef2, k2, dx2, dtype):
     """Backward apply (no ReLU) of two BatchNorms fed by the same dy: dy read
     once (vu_bn_bwd_apply2).  False when the layout is not served."""
