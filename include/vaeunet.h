@@ -671,6 +671,32 @@ int vu_kl_free_bits(const float* mu, const float* logvar, int B, int L,
                     float free_bits, float* value, float* gmu, float* glogvar,
                     void* stream);
 
+/* ---- focal + Dice (MAFocalLoss / MASegmentationLoss, loss.py:66-111) ---- */
+/* Elementwise over n fp32 logits x and targets t in [0, 1]:
+ *   b = t*sp(-x) + (1-t)*sp(x), sp(z) = max(z,0) + log1p(exp(-|z|))
+ *   f = (alpha*t + (1-alpha)*(1-t)) * (1 - exp(-b))^gamma * b
+ *   focal = sum f (sum_reduction) or sum f / n
+ *   dice_loss = 1 - (2*sum p t + smooth) /
+ *               (max(sum p, smooth/2) + max(sum t, smooth/2) + smooth), p = sigmoid(x)
+ * sums[0..4] = {sum f, sum p*t, sum p, sum t, number of NaN logits} (fp64,
+ * fixed summation order); loss[0] = w_focal*focal + w_dice*dice_loss and
+ * parts = {focal, dice_loss} (both optional).  A NaN logit adds p = 0 and
+ * f = 0 and still counts in n.  gamma must be 0 or >= 1, alpha in [0, 1],
+ * smooth > 0 (hipErrorInvalidValue otherwise).  The pointers need 4-byte
+ * alignment only.  workspace: vu_focal_workspace_bytes */
+int64_t vu_focal_workspace_bytes(void);
+int vu_focal_dice_fwd(const float* logits, const float* target, int64_t n,
+                      float alpha, float gamma, float smooth, float w_focal,
+                      float w_dice, int sum_reduction, double* sums,
+                      float* loss, float* parts, double* workspace,
+                      void* stream);
+/* grad = g * d loss / d logits with the sums of vu_focal_dice_fwd,
+ * g = *gscale (a device scalar; NULL = 1); 0 at a NaN logit */
+int vu_focal_dice_bwd(const float* logits, const float* target, int64_t n,
+                      float alpha, float gamma, float smooth, float w_focal,
+                      float w_dice, int sum_reduction, const double* sums,
+                      const float* gscale, float* grad, void* stream);
+
 /* dice_score (utils/metrics.py:8-35): a = x > 0.5, b = t > 0.5 over n
  * elements; *score = 1 if sum a + sum b == 0 else (2*sum(a*b) + epsilon) /
  * (sum a + sum b + epsilon), computed on the device (no host sync; the

@@ -179,6 +179,9 @@ _SIGS = {
     "vu_loss_workspace_bytes": (_l, []),
     "vu_bce_dice_fwd2": (_i, [_p, _p, _l, _p, _f, _f, _f, _p, _p, _p, _p]),
     "vu_bce_dice_bwd": (_i, [_p, _p, _l, _p, _f, _f, _f, _p, _p, _p]),
+    "vu_focal_workspace_bytes": (_l, []),
+    "vu_focal_dice_fwd": (_i, [_p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p]),
+    "vu_focal_dice_bwd": (_i, [_p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p]),
     "vu_kl_free_bits2": (_i, [_p, _p, _i, _i, _f, _p, _p, _p, _p, _p]),
     "vu_sumsq": (_i, [_p, _l, _p, _p, _p]),
     "vu_dice_score": (_i, [_p, _p, _l, _f, _p, _p, _p, _p]),

@@ -8,6 +8,11 @@ device and the backward is one elementwise kernel — no host synchronisation
 (the reference's ``isnan().any()`` check at loss.py:12 becomes a per-element
 NaN->0 inside the kernel, which is what its nan_to_num achieves).
 
+MAFocalLoss / MASegmentationLoss (loss.py:66-111, the ``--lesion-type MA``
+objective) run on the fused focal + Dice kernels of csrc/focal.hip; their
+definitions are written out in DESIGN.md §4.7 and are unpinned against the
+reference, so every constant is a constructor argument.
+
 Deviation, documented: the reference's ``.view(-1)`` (loss.py:17-18) raises on
 channels_last logits with more than one class; here the sums are taken in
 memory order, which equals the reference's result whenever it runs.
@@ -100,6 +105,123 @@ class CombinedLoss(nn.Module):
 
     def forward(self, inputs, targets):
         loss, parts = _combined(inputs, targets, 1.0, self.bce_weight, self.dice_weight)
+        self.last_parts = parts
+        return loss
+
+
+# ---- focal + Dice (MAFocalLoss / MASegmentationLoss) --------------------------
+def _check_focal_cfg(alpha, gamma, smooth, reduction):
+    """Host-side validation, before any tensor is looked at."""
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"alpha must be in [0, 1], got {alpha}")
+    g = float(gamma)
+    if not (g == 0.0 or g >= 1.0):
+        raise ValueError(f"gamma must be 0 or >= 1 (between them the gradient is unbounded at b -> 0), got {gamma}")
+    if not float(smooth) > 0.0:
+        raise ValueError(f"smooth must be > 0, got {smooth}")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+
+
+def _focal_pair(inputs, targets):
+    """_dense_pair with the shapes compared first (a mismatch is a ValueError
+    on any device) and empty tensors refused."""
+    if tuple(targets.shape) != tuple(inputs.shape):
+        raise ValueError(f"target shape {tuple(targets.shape)} != input shape {tuple(inputs.shape)}")
+    x, t = _dense_pair(inputs, targets)
+    if x.numel() == 0:
+        raise ValueError("focal_dice_loss: empty input")
+    return x, t
+
+
+def _focal_fwd(x, t, cfg):
+    """The two forward launches: (loss, parts [focal, dice_loss], sums fp64 [5])."""
+    alpha, gamma, smooth, w_focal, w_dice, sum_reduction = cfg
+    sums = torch.empty(5, dtype=torch.float64, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    parts = torch.empty(2, dtype=torch.float32, device=x.device)
+    ws = torch.empty(query("vu_focal_workspace_bytes") // 8, dtype=torch.float64, device=x.device)
+    call("vu_focal_dice_fwd", ptr(x), ptr(t), x.numel(), alpha, gamma, smooth, w_focal, w_dice, sum_reduction,
+         ptr(sums), ptr(loss), ptr(parts), ptr(ws), stream())
+    return loss, parts, sums
+
+
+def _focal_bwd(x, t, sums, gout, cfg):
+    alpha, gamma, smooth, w_focal, w_dice, sum_reduction = cfg
+    g = gout.float().contiguous()
+    grad = torch.empty_like(x)
+    call("vu_focal_dice_bwd", ptr(x), ptr(t), x.numel(), alpha, gamma, smooth, w_focal, w_dice, sum_reduction,
+         ptr(sums), ptr(g), ptr(grad), stream())
+    return grad
+
+
+class _FocalDice(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, cfg):
+        loss, parts, sums = _focal_fwd(x, t, cfg)
+        ctx.save_for_backward(x, t, sums)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, gout, _gparts):
+        if gout is None:
+            return None, None, None
+        x, t, sums = ctx.saved_tensors
+        return _focal_bwd(x, t, sums, gout, ctx.cfg), None, None
+
+
+def _focal_dice(inputs, targets, alpha, gamma, smooth, w_focal, w_dice, reduction):
+    _check_focal_cfg(alpha, gamma, smooth, reduction)
+    x, t = _focal_pair(inputs, targets)
+    cfg = (float(alpha), float(gamma), float(smooth), float(w_focal), float(w_dice), int(reduction == "sum"))
+    return _FocalDice.apply(x, t, cfg)
+
+
+def focal_dice_loss(inputs, targets, alpha=0.75, gamma=2.0, smooth=1.0, focal_weight=0.5, dice_weight=0.5,
+                    reduction="mean"):
+    """focal_weight * focal + dice_weight * dice_loss in one fused pass:
+    focal = mean | sum of a_t * (1 - exp(-b))**gamma * b, b = BCEWithLogits(x, t),
+    a_t = alpha * t + (1 - alpha) * (1 - t); dice_loss as ``dice_loss``.  Any
+    shape, soft targets allowed; a NaN logit adds nothing and gets gradient 0."""
+    return _focal_dice(inputs, targets, alpha, gamma, smooth, focal_weight, dice_weight, reduction)[0]
+
+
+class MAFocalLoss(nn.Module):
+    """The focal term alone (loss.py:66-92)."""
+
+    def __init__(self, alpha=0.75, gamma=2.0, reduction="mean"):
+        super().__init__()
+        _check_focal_cfg(alpha, gamma, 1.0, reduction)
+        self.alpha = alpha
+        self.gamma = gamma
+        self.reduction = reduction
+
+    def forward(self, inputs, targets):
+        return _focal_dice(inputs, targets, self.alpha, self.gamma, 1.0, 1.0, 0.0, self.reduction)[0]
+
+
+class MASegmentationLoss(nn.Module):
+    """focal_weight * MAFocalLoss(mean) + dice_weight * dice_loss (loss.py:95-111).
+
+    After a call, ``self.last_parts`` holds the device tensor [focal,
+    dice_loss] (for logging without an extra pass)."""
+
+    def __init__(self, focal_weight=0.5, dice_weight=0.5, alpha=0.75, gamma=2.0, smooth=1.0):
+        super().__init__()
+        _check_focal_cfg(alpha, gamma, smooth, "mean")
+        self.focal_weight = focal_weight
+        self.dice_weight = dice_weight
+        self.alpha = alpha
+        self.gamma = gamma
+        self.smooth = smooth
+        self.last_parts = None
+
+    def forward(self, inputs, targets):
+        loss, parts = _focal_dice(inputs, targets, self.alpha, self.gamma, self.smooth, self.focal_weight,
+                                  self.dice_weight, "mean")
         self.last_parts = parts
         return loss
 

@@ -27,6 +27,7 @@ Reference ops each one replaces:
   attn_gate_fwd / _bwd           AttentionGate (train-mode BatchNorms)  unet_parts.py:7-30
   vae_bottleneck_fwd / _bwd      mu/logvar heads + reparameterize   unet_resnet.py:140-147,191-194
   bce_dice_loss                  CombinedLoss.forward             utils/loss.py:45-63
+  focal_dice_loss                MASegmentationLoss / MAFocalLoss forward  utils/loss.py:66-111
   seg_counts                     F.interpolate + (x > 0.5) + the TP/FP/FN/TN sums of evaluate.py /
                                  utils/metrics.py get_all_metrics (integer output, not differentiable)
   calib_hist                     the histogram / sum passes of utils/uncertainty_metrics.py (ECE, Brier,
@@ -44,7 +45,7 @@ from . import calibration as _calibration
 from . import metrics as _metrics
 from ._lib import call, ptr, query, stream
 from .engine import conv_layout, convT_layout, w3x3_dgrad, w3x3_fwd, wT_dgrad, wT_fwd
-from .loss import _dense_pair
+from .loss import _check_focal_cfg, _dense_pair, _focal_bwd, _focal_fwd, _focal_pair
 
 _NS = "vaeunet"
 
@@ -302,6 +303,49 @@ def _loss_backward(ctx, g, _gsums):
 
 
 bce_dice_loss.register_autograd(_loss_backward, setup_context=_loss_setup)
+
+
+# ---- focal + Dice (MAFocalLoss / MASegmentationLoss) ---------------------------------
+def _focal_cfg(alpha, gamma, smooth, w_focal, w_dice, sum_reduction):
+    _check_focal_cfg(alpha, gamma, smooth, "sum" if sum_reduction else "mean")
+    return (float(alpha), float(gamma), float(smooth), float(w_focal), float(w_dice), int(bool(sum_reduction)))
+
+
+@torch.library.custom_op(f"{_NS}::focal_dice_loss", mutates_args=(), device_types="cuda")
+def focal_dice_loss(logits: torch.Tensor, target: torch.Tensor, alpha: float, gamma: float, smooth: float,
+                    w_focal: float, w_dice: float, sum_reduction: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """w_focal * focal(mean | sum) + w_dice * (1 - soft Dice) in one fused
+    reduction (vaeunet_amd.loss.focal_dice_loss; fp64 block sums, loss formed
+    on the device, no host sync).  Returns (loss, sums): sums = the fp64
+    {sum f, sum p*t, sum p, sum t, NaN logits} the backward uses."""
+    cfg = _focal_cfg(alpha, gamma, smooth, w_focal, w_dice, sum_reduction)
+    x, t = _focal_pair(logits, target)
+    loss, _, sums = _focal_fwd(x, t, cfg)
+    return loss, sums
+
+
+@focal_dice_loss.register_fake
+def _(logits, target, alpha, gamma, smooth, w_focal, w_dice, sum_reduction):
+    _focal_cfg(alpha, gamma, smooth, w_focal, w_dice, sum_reduction)
+    if tuple(target.shape) != tuple(logits.shape):
+        raise ValueError(f"target shape {tuple(target.shape)} != input shape {tuple(logits.shape)}")
+    return (torch.empty((), dtype=torch.float32, device=logits.device),
+            torch.empty(5, dtype=torch.float64, device=logits.device))
+
+
+def _focal_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], output[1])
+    ctx.cfg = inputs[2:]
+
+
+def _focal_backward(ctx, g, _gsums):
+    logits, target, sums = ctx.saved_tensors
+    x, t = _dense_pair(logits, target)
+    grad = _focal_bwd(x, t, sums, g, _focal_cfg(*ctx.cfg))
+    return grad.to(logits.dtype), None, None, None, None, None, None, None
+
+
+focal_dice_loss.register_autograd(_focal_backward, setup_context=_focal_setup)
 
 # ---- BatchNorm2d statistics ------------------------------------------------------
 @torch.library.custom_op(f"{_NS}::bn_finalize", mutates_args=(), device_types="cuda")
@@ -675,4 +719,4 @@ def _(prob, target, uncertainty=None, n_bins=15, u_max=0.6931471805599453):
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
-       "bce_dice_loss", "seg_counts", "calib_hist")
+       "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist")
