@@ -125,7 +125,10 @@ __global__ void kl_kernel(const float* mu, const float* lv, int B, int L, float 
       float s = g * cmask * mmask / (float)B;
       bool fm = isfinite(mu[i]), fv = isfinite(lv[i]);
       gmu[i] = fm ? s * m : 0.f;
-      glv[i] = fv ? s * 0.5f * (expf(v) - 1.f) : 0.f;
+      // a non-finite logvar gets its gradient times 0 (nan_to_num's backward is
+      // grad * isfinite): 0, except NaN at +inf, where grad is already 0 * inf
+      const float dv = s * 0.5f * (expf(v) - 1.f);
+      glv[i] = fv ? dv : dv * 0.f;
     }
   }
   acc = block_sum_d(acc, sh);
