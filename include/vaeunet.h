@@ -1088,6 +1088,33 @@ int vu_patch_stats(const float* img, int C, int H, int W, const float* mask,
                    int P, int stride, int ny, int nx, int* black, int* lesion,
                    void* stream);
 
+/* Training augmentation of a patch batch in one launch: image
+ * img [B][H][W][C = 3] and mask msk [B][H][W][Cm >= 1] (NHWC fp32) -> out_img,
+ * out_msk of the same shapes (no aliasing with the inputs).  Output pixel
+ * (i, j) of sample b reads the source at
+ *   u = gx_b(j), v = gy_b(i)          piecewise-linear through the S + 1 knots
+ *                                     gx [B][S+1] / gy [B][S+1] over the S equal
+ *                                     cells of [0, W-1] / [0, H-1], 1 <= S <= 32
+ *                                     (S = 1, knots {0, size-1}: the identity, exactly)
+ *   sx = a0 u + a1 v + a2, sy = a3 u + a4 v + a5
+ * image: bilinear, a + t (b - a) per axis; mask: nearest, floor(s + 0.5).
+ * border 0 = constant (taps outside read 0), 1 = reflect101 (index folded with
+ * period 2 (size - 1)).  Coordinates are clamped to +-2^20 first: no parameter
+ * value addresses outside the sample.  Then, image only: v = powf(max(v, 0), g)
+ * unless g == 1; v = M v + o; v += sigma n unless sigma == 0 (n: Box-Muller on
+ * Philox4x32-10 with key = seed, counter = (pixel index lo, hi, b, offset),
+ * first three normals -> R, G, B; independent of B and the launch geometry);
+ * clip to [0, 1].  params [B][20] fp32 = a0..a5, g, M (row-major 3 x 3), o (3),
+ * sigma; all tables in device memory.
+ * hipErrorInvalidValue, nothing launched: C != 3, Cm < 1, S outside 1..32,
+ * unknown border, negative sizes, a null pointer, B > 65535, H or W > 32768.
+ * B, H or W == 0: returns 0, nothing launched. */
+int vu_augment_patch(const float* img, const float* msk, int B, int H, int W,
+                     int C, int Cm, const float* params, const float* gx,
+                     const float* gy, int S, int border, uint64_t seed,
+                     uint32_t offset, float* out_img, float* out_msk,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

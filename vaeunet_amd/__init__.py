@@ -6,6 +6,8 @@ Drop-in surface (same names / signatures / state_dict keys as the reference):
   iou_score, precision_recall, specificity, accuracy, get_all_metrics}, evaluate.evaluate
 Calibration / uncertainty metrics (utils/uncertainty_metrics.py's numbers; unpinned):
   calibration.{calib_hist, calib_metrics, CalibrationMeter}
+Patch loader with device-side training augmentation (unpinned):
+  data.{PatchCache, TrainAugment, augment_patches}
 Dispatcher ops: torch.ops.vaeunet.* (vaeunet_amd.ops)
 """
 from .unet_model import UNet  # noqa: F401

@@ -233,6 +233,7 @@ _SIGS = {
     "vu_uncertainty": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _p]),
     "vu_gather_affine": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
     "vu_patch_stats": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "vu_augment_patch": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, C.c_uint64, C.c_uint32, _p, _p, _p]),
 }
 
 _lib = None

@@ -24,13 +24,20 @@ it to the device as channels_last (train.py:382-383).
 ``PatchCache`` reads the same files (``torch.load(weights_only=True)``: no
 code is unpickled) with a thread pool, stages each batch in pinned host
 memory, copies it to the GPU on a side stream (overlapping the step that is
-running) and applies the GEOMETRIC part of the reference's training
-augmentation (utils/data_loading.py:116-120: HorizontalFlip, VerticalFlip,
-RandomRotate90, each p = 0.5, applied to image and mask alike) on the device
-in one gather launch per tensor (``vu_gather_affine``).  The photometric and
-elastic transforms (CLAHE, gamma, colour jitter, affine, noise, blur, grid
-distortion; :121-178) come from albumentations, which is absent here: out of
-scope.  Normalize(mean=0, std=1) of train.py:37 is the identity.
+running) and augments it on the device.  ``augment=True`` applies the
+flip / rot90 part of the reference's training transform
+(utils/data_loading.py:116-120: HorizontalFlip, VerticalFlip, RandomRotate90,
+each p = 0.5, applied to image and mask alike) in one integer gather launch
+per tensor (``vu_gather_affine``).  ``augment=TrainAugment(...)`` applies the
+whole device-side transform in ONE launch per batch (``vu_augment_patch``,
+DESIGN.md §4.8): flips, rot90, small-angle affine and grid distortion as one
+resampling of image (bilinear) and mask (nearest), then gamma, brightness /
+contrast / saturation / hue as one colour matrix, Gaussian noise (Philox) and
+the clip to [0, 1].  The reference takes these from albumentations
+(:121-178), which is absent here, so the transforms are defined in §4.8 and
+their ranges are ``TrainAugment``'s arguments: unpinned vs the reference.
+CLAHE and blur (a histogram pass, a neighbourhood pass) stay out of scope.
+Normalize(mean=0, std=1) of train.py:37 is the identity.
 """
 import logging
 import os
@@ -168,8 +175,8 @@ class IDRIDDataset(torch.utils.data.Dataset):
     of the window statistics), same cache directory
     (``base_dir/patches/split/lesion_type``, cleared first), same
     ``patch_indices`` and ``__getitem__`` records.  ``transform`` is None:
-    the photometric augmentations are albumentations (absent); the geometric
-    flips / rot90 run on the device in ``PatchCache(augment=True)``."""
+    the reference's albumentations pipeline is absent; augmentation runs on
+    the device in ``PatchCache(augment=True | TrainAugment(...))``."""
 
     def __init__(self, base_dir, split="train", scale=0.25, patch_size=None, lesion_type="EX", max_images=None,
                  skip_border_check=False, ids=None, rng=None, device="cuda"):
@@ -243,13 +250,228 @@ def _flip_rot_map(P, hflip, vflip, k):
     return [ay, by, cy, ax, bx, cx]
 
 
+# ----------------------------------------------------------------------------
+# training augmentation: host-side parameters, one launch
+# ----------------------------------------------------------------------------
+NPARAM = 20                       # a0..a5, gamma, M (9), o (3), sigma
+MAX_GRID_STEPS = 32
+BORDERS = {"constant": 0, "reflect101": 1}
+
+_GREY = np.array([0.299, 0.587, 0.114])
+_YIQ = np.array([[0.299, 0.587, 0.114], [0.5959, -0.2746, -0.3213], [0.2115, -0.5227, 0.3112]])
+# generator of the rotation about the grey axis, in RGB: inv(YIQ) [[0,0,0],[0,0,-1],[0,1,0]] YIQ
+_HUE_J = np.linalg.inv(_YIQ) @ np.array([[0.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]]) @ _YIQ
+_ROT90 = np.array([[0.0, -1.0], [1.0, 0.0]])   # one np.rot90 as an output -> source map of centred (x, y)
+
+
+def affine_matrix(H, W, hflip=False, vflip=False, k=0, angle=0.0, scale=1.0, shift=(0.0, 0.0)):
+    """The six fp32 values (a0..a5) of the output -> source map sx = a0 x + a1 y
+    + a2, sy = a3 x + a4 y + a5 of: HorizontalFlip, VerticalFlip, rot90(k)
+    (numpy's counter-clockwise), then a rotation by ``angle`` degrees, an
+    isotropic zoom by ``scale`` and a shift by ``shift`` = (fraction of W,
+    fraction of H), everything about the patch centre ((W-1)/2, (H-1)/2).
+    The last step reads source = R(angle) (output - shift) / scale in centred
+    coordinates, R(t) = [[cos t, -sin t], [sin t, cos t]].  Flips and rot90
+    alone give exact integers (square patches for odd k)."""
+    if not scale > 0:
+        raise ValueError(f"scale must be positive, got {scale}")
+    th = np.deg2rad(float(angle))
+    L = np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]]) / float(scale)
+    t = -L @ np.array([float(shift[0]) * W, float(shift[1]) * H])
+    front = np.diag([-1.0 if hflip else 1.0, -1.0 if vflip else 1.0]) @ np.linalg.matrix_power(_ROT90, int(k) % 4)
+    L, t = front @ L, front @ t
+    c = np.array([(W - 1) / 2.0, (H - 1) / 2.0])
+    off = c - L @ c + t
+    return np.array([L[0, 0], L[0, 1], off[0], L[1, 0], L[1, 1], off[1]], dtype=np.float32)
+
+
+def colour_matrix(brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0):
+    """(M [3, 3], o [3]) fp32 of v <- M v + o for, in this order: v + brightness;
+    (1 + contrast) (v - 0.5) + 0.5; grey + (1 + saturation) (v - grey) with
+    grey = 0.299 R + 0.587 G + 0.114 B; a rotation by ``hue`` turns about the
+    grey axis in YIQ.  All four zero give the identity exactly."""
+    b, c, s = float(brightness), float(contrast), float(saturation)
+    th = 2.0 * np.pi * float(hue)
+    eye, G = np.eye(3), np.tile(_GREY, (3, 1))
+    M, o = (1.0 + c) * eye, np.full(3, (1.0 + c) * b + 0.5 * (1.0 - (1.0 + c)))
+    Ms = (1.0 + s) * eye + (0.0 - s) * G
+    Mh = eye + (np.cos(th) - 1.0) * (eye - G) + np.sin(th) * _HUE_J
+    M, o = Mh @ Ms @ M, Mh @ Ms @ o
+    return (M + 0.0).astype(np.float32), (o + 0.0).astype(np.float32)
+
+
+def identity_knots(B, size, S=1):
+    """[B, S+1] fp32 knot tables of the identity map over [0, size-1]."""
+    k = (np.arange(S + 1, dtype=np.float64) * (size - 1) / S).astype(np.float32)
+    k[-1] = size - 1
+    return np.tile(k, (B, 1))
+
+
+def identity_params(B):
+    """[B, 20] fp32: identity affine, gamma 1, identity colour, no noise."""
+    p = np.zeros((B, NPARAM), np.float32)
+    p[:, [0, 4, 6, 7, 11, 15]] = 1.0
+    return p
+
+
+class TrainAugment:
+    """Probabilities and ranges of the device-side training transform
+    (``PatchCache(augment=TrainAugment(...))``).  The defaults are this
+    project's own choice of a moderate setting, NOT the reference's
+    albumentations values (unpinned vs the reference); pass
+    the ranges of the run being reproduced.
+
+    geometry   p_hflip, p_vflip, p_rot90 (k uniform in 0..3; square patches);
+               p_affine with rotate_limit (degrees), scale_limit (scale in
+               [1 - l, 1 + l]), shift_limit (fraction of the size, per axis);
+               p_grid with grid_steps (1..32) and grid_limit (< 1)
+    photometry p_gamma with gamma_range; p_colour with brightness_limit,
+               contrast_limit, saturation_limit, hue_limit (turns);
+               p_noise with noise_sigma range
+    border     'reflect101' or 'constant'"""
+
+    def __init__(self, p_hflip=0.5, p_vflip=0.5, p_rot90=0.5, p_affine=0.5, rotate_limit=15.0, scale_limit=0.1,
+                 shift_limit=0.0625, p_grid=0.3, grid_steps=5, grid_limit=0.3, p_gamma=0.3, gamma_range=(0.8, 1.25),
+                 p_colour=0.5, brightness_limit=0.2, contrast_limit=0.2, saturation_limit=0.2, hue_limit=0.02,
+                 p_noise=0.3, noise_sigma=(0.005, 0.03), border="reflect101"):
+        if border not in BORDERS:
+            raise ValueError(f"border must be one of {sorted(BORDERS)}, got {border!r}")
+        if not 1 <= int(grid_steps) <= MAX_GRID_STEPS:
+            raise ValueError(f"grid_steps must be in [1, {MAX_GRID_STEPS}], got {grid_steps}")
+        if not 0 <= grid_limit < 1:
+            raise ValueError(f"grid_limit must be in [0, 1) (cell widths 1 +- limit stay positive), got {grid_limit}")
+        if not 0 <= scale_limit < 1:
+            raise ValueError(f"scale_limit must be in [0, 1), got {scale_limit}")
+        if not (0 < gamma_range[0] <= gamma_range[1]) or not (0 <= noise_sigma[0] <= noise_sigma[1]):
+            raise ValueError("gamma_range must be positive and noise_sigma non-negative, both ascending")
+        self.p_hflip, self.p_vflip, self.p_rot90, self.p_affine = p_hflip, p_vflip, p_rot90, p_affine
+        self.rotate_limit, self.scale_limit, self.shift_limit = rotate_limit, scale_limit, shift_limit
+        self.p_grid, self.grid_steps, self.grid_limit = p_grid, int(grid_steps), grid_limit
+        self.p_gamma, self.gamma_range = p_gamma, tuple(gamma_range)
+        self.p_colour, self.brightness_limit, self.contrast_limit = p_colour, brightness_limit, contrast_limit
+        self.saturation_limit, self.hue_limit = saturation_limit, hue_limit
+        self.p_noise, self.noise_sigma = p_noise, tuple(noise_sigma)
+        self.border = border
+
+    def _knots(self, size, S, rng):
+        w = 1.0 + rng.uniform(-self.grid_limit, self.grid_limit, S)
+        cum = np.concatenate([[0.0], np.cumsum(w)])
+        k = (cum / cum[-1] * (size - 1)).astype(np.float32)
+        k[0], k[-1] = 0.0, size - 1
+        return k
+
+    def draw(self, B, H, W, rng):
+        """Host arrays (params [B, 20], gx [B, S+1], gy [B, S+1]) fp32 for one
+        batch from the numpy Generator ``rng``; a transform whose coin fails
+        contributes its identity.  S = grid_steps (1 when p_grid is 0)."""
+        if self.p_rot90 > 0 and H != W:
+            raise ValueError("rot90 augmentation needs square patches")
+        S = self.grid_steps if self.p_grid > 0 else 1
+        params = identity_params(B)
+        gx, gy = identity_knots(B, W, S), identity_knots(B, H, S)
+        for b in range(B):
+            hf = rng.random() < self.p_hflip
+            vf = rng.random() < self.p_vflip
+            k = int(rng.integers(0, 4)) if rng.random() < self.p_rot90 else 0
+            angle, scale, shift = 0.0, 1.0, (0.0, 0.0)
+            if rng.random() < self.p_affine:
+                angle = rng.uniform(-self.rotate_limit, self.rotate_limit)
+                scale = 1.0 + rng.uniform(-self.scale_limit, self.scale_limit)
+                shift = (rng.uniform(-self.shift_limit, self.shift_limit),
+                         rng.uniform(-self.shift_limit, self.shift_limit))
+            params[b, 0:6] = affine_matrix(H, W, hf, vf, k, angle, scale, shift)
+            if rng.random() < self.p_grid:
+                gx[b], gy[b] = self._knots(W, S, rng), self._knots(H, S, rng)
+            if rng.random() < self.p_gamma:
+                params[b, 6] = rng.uniform(*self.gamma_range)
+            if rng.random() < self.p_colour:
+                M, o = colour_matrix(rng.uniform(-self.brightness_limit, self.brightness_limit),
+                                     rng.uniform(-self.contrast_limit, self.contrast_limit),
+                                     rng.uniform(-self.saturation_limit, self.saturation_limit),
+                                     rng.uniform(-self.hue_limit, self.hue_limit))
+                params[b, 7:16], params[b, 16:19] = M.reshape(9), o
+            if rng.random() < self.p_noise:
+                params[b, 19] = rng.uniform(*self.noise_sigma)
+        return params, gx, gy
+
+
+def _check_augment_args(img, msk, params, gx, gy, seed, offset, border):
+    """Host validation of one augmentation call; returns (params, gx, gy) as
+    contiguous fp32 numpy arrays.  Nothing here touches a device."""
+    if border not in BORDERS:
+        raise ValueError(f"border must be one of {sorted(BORDERS)}, got {border!r}")
+    if img.dim() != 4 or msk.dim() != 4 or img.shape[1] != 3 or msk.shape[1] < 1:
+        raise ValueError(f"expected image [B, 3, H, W] and mask [B, Cm >= 1, H, W], got {tuple(img.shape)} and "
+                         f"{tuple(msk.shape)}")
+    B, _, H, W = img.shape
+    if msk.shape[0] != B or tuple(msk.shape[2:]) != (H, W):
+        raise ValueError(f"image {tuple(img.shape)} and mask {tuple(msk.shape)} differ in batch or size")
+    if img.dtype != torch.float32 or msk.dtype != torch.float32:
+        raise ValueError("image and mask must be float32")
+    if H < 2 or W < 2:
+        raise ValueError(f"patches must be at least 2 x 2, got {H} x {W}")
+    params, gx, gy = (np.ascontiguousarray(a, dtype=np.float32) for a in (params, gx, gy))
+    if params.shape != (B, NPARAM):
+        raise ValueError(f"params must be [{B}, {NPARAM}], got {params.shape}")
+    if gx.ndim != 2 or gx.shape != gy.shape or gx.shape[0] != B or not 2 <= gx.shape[1] <= MAX_GRID_STEPS + 1:
+        raise ValueError(f"gx and gy must both be [{B}, S + 1] with 1 <= S <= {MAX_GRID_STEPS}, got {gx.shape} "
+                         f"and {gy.shape}")
+    for name, a in (("params", params), ("gx", gx), ("gy", gy)):
+        if not np.isfinite(a).all():
+            raise ValueError(f"{name} holds a non-finite value")
+    for name, a in (("gx", gx), ("gy", gy)):
+        if not (np.diff(a, axis=1) > 0).all():
+            raise ValueError(f"{name}: the knots of every sample must be strictly increasing")
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(offset) < 2 ** 32:
+        raise ValueError(f"seed must fit 64 bits and offset 32 bits, got {seed} and {offset}")
+    return params, gx, gy
+
+
+def _launch_augment(img, msk, dparams, dgx, dgy, seed, offset, border):
+    """The one vu_augment_patch launch on device tensors (border: the C code)."""
+    img = img.contiguous(memory_format=CL)
+    msk = msk.contiguous(memory_format=CL)
+    B, _, H, W = img.shape
+    Cm, S = msk.shape[1], dgx.shape[1] - 1
+    oimg = K.empty_act(B, 3, H, W, torch.float32, img.device)
+    omsk = K.empty_act(B, Cm, H, W, torch.float32, img.device)
+    with torch.cuda.device(img.device):
+        K.call("vu_augment_patch", K.ptr(img), K.ptr(msk), B, H, W, 3, Cm, K.ptr(dparams), K.ptr(dgx), K.ptr(dgy), S,
+               border, int(seed), int(offset), K.ptr(oimg), K.ptr(omsk), K.stream())
+    return oimg, omsk
+
+
+def augment_patches(img, msk, params, gx, gy, seed, offset=0, border="reflect101"):
+    """Augment image [B, 3, H, W] and mask [B, Cm, H, W] (fp32 on the device) in
+    ONE launch (vu_augment_patch) with the host arrays of
+    ``TrainAugment.draw`` (or any of the same layout); returns (image, mask),
+    channels_last on the device.  The arrays are checked here before they are
+    uploaded (finite, consistent shapes, increasing knots: ValueError); the
+    kernel's coordinate clamp is the second line of defence.  The noise is a
+    function of (seed, offset, sample, pixel) alone."""
+    params, gx, gy = _check_augment_args(img, msk, params, gx, gy, seed, offset, border)
+    if img.device.type != "cuda" or msk.device != img.device:
+        raise RuntimeError(f"augment_patches runs on MI355X (HIP) devices only; got {img.device} and {msk.device}")
+    B, S1 = params.shape[0], gx.shape[1]
+    host = torch.from_numpy(np.concatenate([params.reshape(-1), gx.reshape(-1), gy.reshape(-1)]))
+    dev = host.to(img.device)                    # one upload for the three tables
+    n0, n1 = B * NPARAM, B * S1
+    return _launch_augment(img, msk, dev[:n0].view(B, NPARAM), dev[n0:n0 + n1].view(B, S1),
+                           dev[n0 + n1:].view(B, S1), seed, offset, BORDERS[border])
+
+
 class PatchCache:
     """Iterate the cached patches in batches on ``device``.
 
     paths: cache files (or a directory holding them); yields dicts with
     ``image`` [B, 3, P, P] and ``mask`` [B, 1, P, P] (fp32, channels_last, on
-    the device), ``img_id`` and ``coords``.  ``augment`` enables the
-    flip/rotate augmentation (seeded: ``seed``)."""
+    the device), ``img_id`` and ``coords``.  ``augment``: False; True for the
+    flip/rotate augmentation alone (one integer gather per tensor); or a
+    ``TrainAugment`` for the full device-side transform (one draw and one
+    launch per batch; the Philox key is ``seed``, the offset the number of
+    batches augmented so far; the batch gains ``aug_params``, what
+    ``augment_patches`` needs to replay it).  All draws come from the
+    generator seeded with ``seed``."""
 
     def __init__(self, paths, batch_size, device="cuda", augment=False, shuffle=False, seed=0, workers=6,
                  drop_last=False):
@@ -260,6 +482,8 @@ class PatchCache:
         self.device = torch.device(device)
         self.augment = augment
         self.shuffle = shuffle
+        self.seed = int(seed)
+        self.aug_calls = 0                                         # Philox offset of the next TrainAugment batch
         self.rng = np.random.Generator(np.random.PCG64(seed))
         self.pool = ThreadPoolExecutor(max_workers=workers)        # file reads
         self.batch_pool = ThreadPoolExecutor(max_workers=1)        # batch assembly (prefetch 1)
@@ -322,6 +546,14 @@ class PatchCache:
             cur.wait_event(ev)
             img.record_stream(cur)   # allocated on the copy stream, used (and freed) on this one
             msk.record_stream(cur)
-            if self.augment:
+            extra = {}
+            if isinstance(self.augment, TrainAugment):
+                params, gx, gy = self.augment.draw(img.shape[0], img.shape[2], img.shape[3], self.rng)
+                aug = {"params": params, "gx": gx, "gy": gy, "seed": self.seed & (2 ** 64 - 1),
+                       "offset": self.aug_calls & 0xffffffff, "border": self.augment.border}
+                img, msk = augment_patches(img, msk, **aug)
+                self.aug_calls += 1
+                extra["aug_params"] = aug
+            elif self.augment:
                 img, msk, _ = self.augment_batch(img, msk)
-            yield {"image": img, "mask": msk, "img_id": ids, "coords": coords}
+            yield {"image": img, "mask": msk, "img_id": ids, "coords": coords, **extra}

@@ -32,6 +32,8 @@ Reference ops each one replaces:
                                  utils/metrics.py get_all_metrics (integer output, not differentiable)
   calib_hist                     the histogram / sum passes of utils/uncertainty_metrics.py (ECE, Brier,
                                  NLL, AUROC / AUPRC, sparsification) as one fused pass
+  augment_patch                  the albumentations training transform of utils/data_loading.py:116-178 (warp,
+                                 colour, noise; DESIGN.md §4.8's definitions) as one launch per batch
 """
 import ctypes as C
 import types
@@ -42,6 +44,7 @@ from . import _lib
 from . import engine as E
 from . import kernels as K
 from . import calibration as _calibration
+from . import data as _data
 from . import metrics as _metrics
 from ._lib import call, ptr, query, stream
 from .engine import conv_layout, convT_layout, w3x3_dgrad, w3x3_fwd, wT_dgrad, wT_fwd
@@ -716,7 +719,47 @@ def _(prob, target, uncertainty=None, n_bins=15, u_max=0.6931471805599453):
             torch.empty(2, **i64)]
 
 
+# ---- training augmentation --------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::augment_patch", mutates_args=(), device_types="cuda")
+def augment_patch(image: torch.Tensor, mask: torch.Tensor, params: torch.Tensor, gx: torch.Tensor,
+                  gy: torch.Tensor, seed: int, offset: int = 0,
+                  reflect: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
+    """vaeunet_amd.data.augment_patches on device tables: image [B, 3, H, W] and
+    mask [B, Cm, H, W] fp32 warped alike (grid distortion + affine; bilinear /
+    nearest; reflect101 or constant border) and the image's gamma / colour
+    matrix / Philox noise / clip, in one launch.  params
+    [B, 20], gx / gy [B, S+1] fp32 on the device (TrainAugment.draw's layout;
+    NOT validated here: the kernel clamps coordinates, use augment_patches for
+    host arrays).  Not differentiable (a data transform)."""
+    _augment_check(image, mask, params, gx, gy)
+    if seed < 0 or not 0 <= offset < 2 ** 32:
+        raise ValueError(f"vaeunet::augment_patch: seed must be non-negative and offset fit 32 bits, got {seed}, "
+                         f"{offset}")
+    return _data._launch_augment(image, mask, params.contiguous(), gx.contiguous(), gy.contiguous(), seed, offset,
+                                 _data.BORDERS["reflect101" if reflect else "constant"])
+
+
+def _augment_check(image, mask, params, gx, gy):
+    B = image.shape[0]
+    if (image.dim() != 4 or mask.dim() != 4 or image.shape[1] != 3 or mask.shape[1] < 1 or mask.shape[0] != B
+            or mask.shape[2:] != image.shape[2:]):
+        raise ValueError(f"vaeunet::augment_patch: expected image [B, 3, H, W] and mask [B, Cm, H, W], got "
+                         f"{tuple(image.shape)} and {tuple(mask.shape)}")
+    if tuple(params.shape) != (B, _data.NPARAM) or gx.dim() != 2 or gx.shape != gy.shape or gx.shape[0] != B \
+            or not 2 <= gx.shape[1] <= _data.MAX_GRID_STEPS + 1:
+        raise ValueError(f"vaeunet::augment_patch: params must be [B, {_data.NPARAM}] and gx, gy [B, S+1] with "
+                         f"1 <= S <= {_data.MAX_GRID_STEPS}")
+    if any(t.dtype != torch.float32 for t in (image, mask, params, gx, gy)):
+        raise ValueError("vaeunet::augment_patch: every tensor must be float32")
+
+
+@augment_patch.register_fake
+def _(image, mask, params, gx, gy, seed, offset=0, reflect=True):
+    _augment_check(image, mask, params, gx, gy)
+    return _cl_empty(*image.shape, image), _cl_empty(*mask.shape, mask)
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
-       "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist")
+       "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch")
