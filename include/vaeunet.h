@@ -242,17 +242,6 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
  *     statistics / stores, fragments read once per group; 5 = non-temporal
  *     output stores, results exact).  Values outside 0..5 are refused. */
 #define VU_TUNE_V6_XM 29
-/*   VU_TUNE_PP_PERSIST: 1 = the ping-pong kernel's 128/256-column tiles as a
- *     persistent walk (one block per CU; the next tile's first halo and
- *     weights stream in during the current tile's epilogue) for grids over
- *     one block per CU, k >= 2 = always, the grid capped at k blocks (tests),
- *     0 (default) = one tile per block. */
-#define VU_TUNE_PP_PERSIST 30
-/*   VU_TUNE_BN_ONEPASS: 1 = vu_bn_bwd_fused runs bf16 tensors of at most
- *     8192 pixels as ONE launch (a block per 8 channels reduces and
- *     applies); 0 (default) = the two-launch path (the one-launch form
- *     measured 12 % slower on config 3: uncoalesced channel slices). */
-#define VU_TUNE_BN_ONEPASS 31
 /*   VU_TUNE_UNSAFE: 1 = allow the experiment modes (VU_TUNE_V6_XM,
  *     VU_TUNE_V7_XM, VU_TUNE_FP8_XM) to be set non-zero; several of them
  *     produce wrong results by design (timing decompositions).  Without it a
@@ -262,7 +251,7 @@ int vu_slab_reduce(const float* slab, int splits, int ni, int nj, int C,
  *     the two wave halves' epilogues staggered into the next tile's first
  *     group (bit-identical results), 0 = the round-5 lock-step kernel. */
 #define VU_TUNE_V6_STAG 34
-/*   Keys 14, 26, 32, 35, 36, 37 are retired, refused
+/*   Keys 14, 26, 30, 31, 32, 35, 36, 37 are retired, refused
  *     (hipErrorInvalidValue): measured-slower variants that were removed.
  *     Do not reuse the numbers. */
 int vu_gemm_set_tuning(int key, int value);
@@ -525,18 +514,6 @@ int vu_maxpool2_bwd(const void* x, int64_t xs, const void* dy, int64_t dys,
 int vu_bn_apply_maxpool2(const void* y, int64_t ys, void* a, int64_t as, void* pool, int64_t ps,
                          int N, int H, int W, int C, const float* scale, const float* shift,
                          int relu, int dtype, void* stream);
-/* BatchNorm(+ReLU) backward THROUGH that 2x2 max-pool: y the BN input, dp
- * the gradient of the pooled output, add the skip gradient of a (or NULL);
- * recomputes a, its first-max argmax and a's gradient per window (as
- * vu_bn_apply_maxpool2 / vu_maxpool2_bwd store them) in a partial pass and an
- * apply pass -> dx (gradient of y); dgamma/dbeta as vu_bn_bwd_reduce, coef
- * [3][C] scratch, workspace vu_reduce_workspace_bytes(N*H*W, C). */
-int vu_bn_bwd_pool_supported(int H, int W, int C, int64_t ys, int64_t dps, int64_t adds, int64_t dxs);
-int vu_bn_bwd_pool(const void* y, int64_t ys, const void* dp, int64_t dps, const void* add, int64_t adds,
-                   int N, int H, int W, int C, const float* scale, const float* shift, const float* mean,
-                   const float* invstd, const float* gamma, int relu, int train, float* dgamma,
-                   float* dbeta, int accumulate, float* coef, float* workspace, void* dx, int64_t dxs,
-                   int dtype, void* stream);
 /* bilinear, align_corners=True, (Hi,Wi) -> (Ho,Wo) placed at (py,px) inside
  * a zero (Hp,Wp) canvas (F.pad of unet_parts.py:88-89 folded in). */
 int vu_upsample_fwd(const void* x, int64_t xs, int N, int Hi, int Wi, int C,

@@ -210,7 +210,7 @@ class _DzRecorder:
         def bn_bwd(dy, xx, coef, bn, relu, M, *a, **kw):
             pre = self.names.get(id(bn))
             if pre is not None:
-                d = (dy.materialize(M) if isinstance(dy, E.PoolGrad) else dy).detach().float()
+                d = dy.detach().float()
                 if relu:
                     C_ = xx.shape[1]
                     d = d * ((xx.float() * coef[0].view(1, C_, 1, 1) + coef[1].view(1, C_, 1, 1)) > 0).float()

@@ -62,7 +62,7 @@ def main():
 
     def bn_bwd(dy, xx, coef, bn, relu, M, *a, **kw):
         pre = bn_name.get(id(bn))
-        if pre is not None and not isinstance(dy, E.PoolGrad):
+        if pre is not None:
             d = dy.detach().float()
             if relu:
                 C = xx.shape[1]

@@ -28,11 +28,11 @@ from vaeunet_amd._lib import BF16, F32, VuConvFp8, VuGemmFwd, VuGemmWgrad, lib  
 # tuning keys (include/vaeunet.h) and their defaults
 V4_MIN_BLOCKS, FP8_GRID, STREAM, V4_SPLITK, V4_SPLIT_CHUNKS, V2_SMALL, V5, V6 = 0, 4, 5, 6, 8, 9, 10, 11
 GEN, SLAB4, BN_NT_MB, V7, V7_NBW, V7_XM, W3_SMALL, FP8_XM, FP8_PP, ATTN = 12, 13, 15, 16, 17, 18, 19, 20, 21, 22
-FP8_C64, FP8_SPLIT, BN_MINBLK, PP_FULL, W2_BIG, V6_XM, PP_PERSIST, BN_ONEPASS = 23, 24, 25, 27, 28, 29, 30, 31
+FP8_C64, FP8_SPLIT, BN_MINBLK, PP_FULL, W2_BIG, V6_XM = 23, 24, 25, 27, 28, 29
 UNSAFE, V6_STAG = 33, 34
 DEFAULTS = {V4_MIN_BLOCKS: 256, FP8_GRID: 0, STREAM: 1, V4_SPLITK: 1, V4_SPLIT_CHUNKS: 2, V2_SMALL: 1, V5: 1, V6: 1,
             GEN: 4, SLAB4: 1, BN_NT_MB: 32, V7: 1, V7_NBW: 3, V7_XM: 0, W3_SMALL: 1, FP8_XM: 0, FP8_PP: 1, ATTN: 1,
-            FP8_C64: 2, FP8_SPLIT: 1, BN_MINBLK: 256, PP_FULL: 1, W2_BIG: 0, V6_XM: 0, PP_PERSIST: 0, BN_ONEPASS: 0,
+            FP8_C64: 2, FP8_SPLIT: 1, BN_MINBLK: 256, PP_FULL: 1, W2_BIG: 0, V6_XM: 0,
             V6_STAG: 1, UNSAFE: 0}
 FWD_IDS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 13)
 

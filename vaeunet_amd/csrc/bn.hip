@@ -559,135 +559,6 @@ __global__ void bn_apply_maxpool_kernel(const T* y, int64_t ys, T* a, int64_t as
   }
 }
 
-// ---- BatchNorm(+ReLU) backward THROUGH the 2x2 max-pool (round 4) ----------
-// The encoder DoubleConvs' BN2 output a = relu(BN(y)) feeds the next Down's
-// max-pool and the decoder's skip concat.  Its backward used to be: max-pool
-// backward (reads a, the skip gradient and the pooled gradient, writes the
-// full-size gradient of a), then the BN backward reduce (reads that gradient
-// and y) and apply (reads both again, writes dy): 8.25 full-size passes.  Here
-// neither a nor its gradient is touched: each pass recomputes, per 2x2
-// window, a = T(relu(fma(y, scale, shift))) exactly as vu_bn_apply_maxpool2
-// stored it, its first-max argmax, and the gradient of a as the max-pool
-// backward stored it, T(skip + [argmax] pooled) -- bit-identical inputs to
-// the BN backward -- from y, the skip gradient and the pooled gradient:
-// 5.5 passes.  A thread owns 8 channels of one pooled pixel (its window).
-struct PoolBnArgs {
-  const void* y; int64_t ys;       // BN input (the conv output), full size
-  const void* dp; int64_t dps;     // gradient of the pooled output
-  const void* add; int64_t adds;   // skip-connection gradient (full size) or null
-  int N, H, W, C;
-  const float* scale; const float* shift; const float* mean; const float* invstd;
-  int relu;
-  float* part;                     // partial pass: [nblk][2][C]
-  const float* coef;               // apply pass: k1, k2, k3 [3][C] (bn_bwd_final)
-  void* dx; int64_t dxs;           // apply pass: gradient of y
-};
-
-template <typename T, bool NT>
-VU_DEV void pool_window(const PoolBnArgs& r, int64_t q, int c, const float (&sc)[8], const float (&sf)[8],
-                        float (&yv)[4][8], float (&dz)[4][8], int64_t& p00) {
-  const int Wo = r.W >> 1, Ho = r.H >> 1;
-  const int j = (int)(q % Wo);
-  const int64_t t = q / Wo;
-  const int i = (int)(t % Ho), n = (int)(t / Ho);
-  p00 = ((int64_t)n * r.H + 2 * i) * r.W + 2 * j;
-  const T* y = reinterpret_cast<const T*>(r.y);
-  const T* ad = reinterpret_cast<const T*>(r.add);
-  Vec8<T> vy[4], va[4], vg;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int64_t pix = p00 + (k >> 1) * r.W + (k & 1);
-    if (NT) vy[k].load_nt(y + pix * r.ys + c); else vy[k].load(y + pix * r.ys + c);
-    if (ad) { if (NT) va[k].load_nt(ad + pix * r.adds + c); else va[k].load(ad + pix * r.adds + c); }
-  }
-  vg.load(reinterpret_cast<const T*>(r.dp) + q * r.dps + c);
-  float best[8];
-  int arg[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; arg[e] = 0; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      yv[k][e] = vy[k].get(e);
-      const float z = fmaf(yv[k][e], sc[e], sf[e]);
-      const float f = rnd<T>(r.relu ? fmaxf(z, 0.f) : z);  // the stored activation
-      if (f > best[e] || isnan(f)) { best[e] = f; arg[e] = k; }
-    }
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float o = ad ? va[k].get(e) : 0.f;
-      if (arg[e] == k) o += vg.get(e);
-      float d = rnd<T>(o);                                   // the stored pool-input gradient
-      if (r.relu && !(fmaf(yv[k][e], sc[e], sf[e]) > 0.f)) d = 0.f;
-      dz[k][e] = d;
-    }
-}
-
-template <typename T, bool NT>
-__global__ void pool_bn_partial_kernel(PoolBnArgs r) {
-  __shared__ float sh[2][256 * 8];
-  ChanMap cm(r.C);
-  const int c = cm.cv * 8;
-  float s0[8], s1[8], sc[8], sf[8], mu[8], is[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    s0[e] = 0.f; s1[e] = 0.f;
-    sc[e] = r.scale[c + e]; sf[e] = r.shift[c + e]; mu[e] = r.mean[c + e]; is[e] = r.invstd[c + e];
-  }
-  const int64_t Q = (int64_t)r.N * (r.H >> 1) * (r.W >> 1);
-  for (int64_t q = (int64_t)blockIdx.x * cm.R + cm.row; q < Q; q += (int64_t)gridDim.x * cm.R) {
-    float yv[4][8], dz[4][8];
-    int64_t p00;
-    pool_window<T, NT>(r, q, c, sc, sf, yv, dz, p00);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        s0[e] += dz[k][e];
-        s1[e] += dz[k][e] * ((yv[k][e] - mu[e]) * is[e]);
-      }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { sh[0][cm.row * r.C + c + e] = s0[e]; sh[1][cm.row * r.C + c + e] = s1[e]; }
-  __syncthreads();
-  for (int cc = threadIdx.x; cc < r.C; cc += 256) {
-    float a0 = 0.f, a1 = 0.f;
-    a0 = lds_sum(&sh[0][cc], cm.R, r.C);
-    a1 = lds_sum(&sh[1][cc], cm.R, r.C);
-    r.part[((int64_t)blockIdx.x * 2 + 0) * r.C + cc] = a0;
-    r.part[((int64_t)blockIdx.x * 2 + 1) * r.C + cc] = a1;
-  }
-}
-
-template <typename T, bool NT>
-__global__ void pool_bn_apply_kernel(PoolBnArgs r) {
-  ChanMap cm(r.C);
-  const int c = cm.cv * 8;
-  float sc[8], sf[8], mu[8], k1[8], k2[8], k3[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    sc[e] = r.scale[c + e]; sf[e] = r.shift[c + e]; mu[e] = r.mean[c + e];
-    k1[e] = r.coef[c + e]; k2[e] = r.coef[r.C + c + e]; k3[e] = r.coef[2 * r.C + c + e];
-  }
-  T* dx = reinterpret_cast<T*>(r.dx);
-  const int64_t Q = (int64_t)r.N * (r.H >> 1) * (r.W >> 1);
-  for (int64_t q = (int64_t)blockIdx.x * cm.R + cm.row; q < Q; q += (int64_t)gridDim.x * cm.R) {
-    float yv[4][8], dz[4][8];
-    int64_t p00;
-    pool_window<T, NT>(r, q, c, sc, sf, yv, dz, p00);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      Vec8<T> vo;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) vo.set(e, k1[e] * dz[k][e] + k2[e] * (yv[k][e] - mu[e]) + k3[e]);
-      vo.store(dx + (p00 + (k >> 1) * r.W + (k & 1)) * r.dxs + c);
-    }
-  }
-}
-
 // ---- BatchNorm forward for SMALL tensors: finalize + apply in one launch ----
 // The ResNet34 encoder's 64^2-16^2 levels (and the U-Net's 32^2 level) have
 // 16-256 partial-statistics tiles; there the two finalize launches and the
@@ -1262,42 +1133,6 @@ extern "C" int vu_bn_apply_maxpool2(const void* y, int64_t ys, void* a, int64_t 
   return (int)hipGetLastError();
 }
 
-// BatchNorm(+ReLU) backward through the 2x2 max-pool: partial pass, fp64
-// finish (dgamma, dbeta, k1..k3 into coef [3][C]), apply pass -> dx (the
-// gradient of y).  1 when served (even H and W, the vectorised channel map).
-extern "C" int vu_bn_bwd_pool_supported(int H, int W, int C, int64_t ys, int64_t dps, int64_t adds, int64_t dxs) {
-  return H % 2 == 0 && W % 2 == 0 && H > 0 && W > 0 && chanmap_ok(C, ys, dps, adds) && dxs % 8 == 0;
-}
-
-extern "C" int vu_bn_bwd_pool(const void* y, int64_t ys, const void* dp, int64_t dps, const void* add, int64_t adds,
-                              int N, int H, int W, int C, const float* scale, const float* shift, const float* mean,
-                              const float* invstd, const float* gamma, int relu, int train, float* dgamma,
-                              float* dbeta, int accumulate, float* coef, float* workspace, void* dx, int64_t dxs,
-                              int dtype, void* stream) {
-  if (!vu_bn_bwd_pool_supported(H, W, C, ys, dps, add ? adds : 8, dxs) || N < 1) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t P = (int64_t)N * H * W;
-  PoolBnArgs r{y, ys, dp, dps, add, adds, N, H, W, C, scale, shift, mean, invstd, relu, workspace, coef, dx, dxs};
-  const int nblk = (int)chan_grid(P, C, RED_MAXBLK);  // rows = pooled pixels: ~4 windows per thread
-  const bool nt = bn_nt(P, C, dtype == VU_BF16 ? 2 : 4);
-  const unsigned agrid = chan_grid(P, C, 8192);
-  if (dtype == VU_BF16) {
-    if (nt) hipLaunchKernelGGL((pool_bn_partial_kernel<bf16_t, true>), dim3(nblk), dim3(256), 0, st, r);
-    else hipLaunchKernelGGL((pool_bn_partial_kernel<bf16_t, false>), dim3(nblk), dim3(256), 0, st, r);
-  } else {
-    hipLaunchKernelGGL((pool_bn_partial_kernel<float, false>), dim3(nblk), dim3(256), 0, st, r);
-  }
-  hipLaunchKernelGGL(bn_bwd_final, dim3((C + 31) / 32), dim3(COLSUM_THREADS), 0, st, workspace, nblk, C, P, gamma,
-                     invstd, dgamma, dbeta, accumulate, coef, train);
-  if (dtype == VU_BF16) {
-    if (nt) hipLaunchKernelGGL((pool_bn_apply_kernel<bf16_t, true>), dim3(agrid), dim3(256), 0, st, r);
-    else hipLaunchKernelGGL((pool_bn_apply_kernel<bf16_t, false>), dim3(agrid), dim3(256), 0, st, r);
-  } else {
-    hipLaunchKernelGGL((pool_bn_apply_kernel<float, false>), dim3(agrid), dim3(256), 0, st, r);
-  }
-  return (int)hipGetLastError();
-}
-
 // Single-launch train-mode BatchNorm forward (finalize + apply [+ residual] [+ ReLU])
 // for small tensors: vu_bn_fwd_fused_supported() says when it applies.
 extern "C" int vu_bn_fwd_fused_supported(int tiles, int C, int64_t ys, int64_t rs, int64_t os) {
@@ -1330,131 +1165,6 @@ extern "C" int vu_bn_fwd_fused(const float* psum, const float* pm2, int tiles, i
 
 // BatchNorm(+ReLU) backward for small tensors in two launches (the partial
 // pass, then the fused fp64 finish + apply) instead of three.
-// ---- one-launch BatchNorm(+ReLU) backward of a small tensor ---------------
-// (P <= ONEPASS_MAXP: ResNet34 layer3 / layer4 and the 32^2 / 16^2 decoder
-// levels of config 3, where the two launches of the fused path were ~7 us
-// each of mostly latency; bf16): one 512-thread block per 8 channels
-// reduces sum dz and sum dz * xhat over all P pixels (thread t: pixels
-// t + 512 k; fp32 per thread, a fixed-order lane butterfly per wave, fp64
-// across the 8 waves), writes dgamma / dbeta and applies dx.  Deterministic;
-// the same per-element formulas as chan_partial_kernel<.., 1> +
-// bn_bwd_fused_apply_kernel.  MEASURED SLOWER (VAE -12 %, off by default,
-// profiles/r5w_ab_bn_onepass.txt): a block per 8 channels of a channels-last
-// tensor reads 16 bytes per 128-byte line per pixel (every line fetched by
-// C / 8 blocks), and wider channel slices leave C / 64 = 4-8 blocks -- the
-// reduction needs the cross-block stage of the two-launch path.
-constexpr int ONEPASS_T = 512, ONEPASS_B = 8, ONEPASS_MAXP = 8192;
-constexpr int ONEPASS_W = ONEPASS_T / 64;
-
-VU_DEV float bfly_sum64(float v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-template <typename T>
-__global__ __launch_bounds__(ONEPASS_T) void bn_bwd_onepass_kernel(BnBwdFusedArgs a) {
-  __shared__ float wsum[2][ONEPASS_W][8];
-  __shared__ float sk[3][8];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int c = blockIdx.x * 8;
-  // 32-bit element offsets from the uniform bases (P * stride < 2^31, host
-  // check) and clamped unconditional loads, ONEPASS_B pixels per thread in
-  // flight; the apply pass re-reads its pixels (L2-resident: <= 256 KB per
-  // block) rather than holding all of them in registers (that spilled)
-  const int P = (int)a.P, dys = (int)a.dys, xs = (int)a.xs;
-  const T* dyc = reinterpret_cast<const T*>(a.dy) + c;
-  const T* xc = reinterpret_cast<const T*>(a.x) + c;
-  float sc[8], sf[8], mu[8], is[8], s0[8], s1[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sc[i] = a.scale[c + i]; sf[i] = a.shift[c + i]; mu[i] = a.mean[c + i]; is[i] = a.invstd[c + i];
-    s0[i] = 0.f; s1[i] = 0.f;
-  }
-  const bool wr = a.accumulate && tid < 8;
-  const float g = tid < 8 ? (a.gamma ? a.gamma[c + tid] : 1.f) : 0.f;
-  const float dg0 = (wr && a.dgamma) ? a.dgamma[c + tid] : 0.f;
-  const float db0 = (wr && a.dbeta) ? a.dbeta[c + tid] : 0.f;
-  for (int p0 = tid; p0 < P; p0 += ONEPASS_T * ONEPASS_B) {
-    Vec8<T> vd[ONEPASS_B], vx[ONEPASS_B];
-#pragma unroll
-    for (int k = 0; k < ONEPASS_B; ++k) {
-      const int p = min(p0 + k * ONEPASS_T, P - 1);
-      vd[k].load(dyc + p * dys);
-      vx[k].load(xc + p * xs);
-    }
-#pragma unroll
-    for (int k = 0; k < ONEPASS_B; ++k) {
-      if (p0 + k * ONEPASS_T >= P) continue;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float xv = vx[k].get(i);
-        float dz = vd[k].get(i);
-        if (a.relu && !(fmaf(xv, sc[i], sf[i]) > 0.f)) dz = 0.f;
-        s0[i] += dz;
-        s1[i] += dz * ((xv - mu[i]) * is[i]);
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float t0 = bfly_sum64(s0[i]), t1 = bfly_sum64(s1[i]);
-    if (lane == 0) {
-      wsum[0][wv][i] = t0;
-      wsum[1][wv][i] = t1;
-    }
-  }
-  __syncthreads();
-  if (tid < 8) {
-    double S0 = 0.0, S1 = 0.0;
-#pragma unroll
-    for (int w = 0; w < ONEPASS_W; ++w) {
-      S0 += (double)wsum[0][w][tid];
-      S1 += (double)wsum[1][w][tid];
-    }
-    const float isc = a.invstd[c + tid];
-    const float k1 = g * isc;
-    sk[0][tid] = k1;
-    sk[1][tid] = a.train ? (float)(-(double)k1 * isc * S1 / (double)a.P) : 0.f;
-    sk[2][tid] = a.train ? (float)(-(double)k1 * S0 / (double)a.P) : 0.f;
-    if (a.dgamma) a.dgamma[c + tid] = a.accumulate ? dg0 + (float)S1 : (float)S1;
-    if (a.dbeta) a.dbeta[c + tid] = a.accumulate ? db0 + (float)S0 : (float)S0;
-  }
-  __syncthreads();
-  float k1[8], k2[8], k3[8];   // block-uniform: scalar registers
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    k1[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sk[0][i])));
-    k2[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sk[1][i])));
-    k3[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sk[2][i])));
-  }
-  T* dxc = reinterpret_cast<T*>(a.dx) + c;
-  const int dxs = (int)a.dxs;
-  for (int p0 = tid; p0 < P; p0 += ONEPASS_T * ONEPASS_B) {
-    Vec8<T> vd[ONEPASS_B], vx[ONEPASS_B];
-#pragma unroll
-    for (int k = 0; k < ONEPASS_B; ++k) {
-      const int p = min(p0 + k * ONEPASS_T, P - 1);
-      vd[k].load(dyc + p * dys);
-      vx[k].load(xc + p * xs);
-    }
-#pragma unroll
-    for (int k = 0; k < ONEPASS_B; ++k) {
-      const int p = p0 + k * ONEPASS_T;
-      if (p >= P) continue;
-      Vec8<T> vo;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float xv = vx[k].get(i);
-        float dz = vd[k].get(i);
-        if (a.relu && !(fmaf(xv, sc[i], sf[i]) > 0.f)) dz = 0.f;
-        vo.set(i, fmaf(k1[i], dz, k2[i] * (xv - mu[i])) + k3[i]);
-      }
-      vo.store(dxc + p * dxs);
-    }
-  }
-}
-
 extern "C" int vu_bn_bwd_fused_supported(int64_t P, int C, int64_t dys, int64_t xs, int64_t dxs) {
   return C % 32 == 0 && chanmap_ok(C, dys, xs) && dxs % 8 == 0 && P >= 1 &&
          (int)chan_grid16(P, C, RED_MAXBLK) <= BNB_FUSED_MAXBLK;
@@ -1466,12 +1176,6 @@ extern "C" int vu_bn_bwd_fused(const void* dy, int64_t dys, const void* x, int64
                                int accumulate, void* dx, int64_t dxs, float* workspace, int dtype, void* stream) {
   if (!vu_bn_bwd_fused_supported(P, C, dys, xs, dxs)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  if (tune(VU_TUNE_BN_ONEPASS) && dtype == VU_BF16 && P <= ONEPASS_MAXP && dys % 8 == 0 && xs % 8 == 0 && P * (dys > xs ? (dys > dxs ? dys : dxs) : (xs > dxs ? xs : dxs)) < ((int64_t)1 << 31)) {
-    BnBwdFusedArgs a{dy, dys, x, xs, P, C, scale, shift, mean, invstd, gamma, relu, train, nullptr, 0,
-                     dgamma, dbeta, accumulate, dx, dxs, 1};
-    hipLaunchKernelGGL(bn_bwd_onepass_kernel<bf16_t>, dim3((unsigned)(C / 8)), dim3(ONEPASS_T), 0, st, a);
-    return (int)hipGetLastError();
-  }
   RedArgs r{dy, dys, x, xs, P, C, scale, shift, mean, invstd, relu, workspace, 0, 0, 0, 0, 0, 0};
   int nblk = 0, rc;
   rc = dtype == VU_BF16 ? launch_partial<bf16_t, 1>(r, st, nblk, BNB_FUSED_MAXBLK)

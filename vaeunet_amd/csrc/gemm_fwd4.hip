@@ -85,11 +85,7 @@ VU_DEV float row16_sum(float v) { return ror_add<1>(ror_add<2>(ror_add<4>(ror_ad
 // registers (VU_TUNE_PP_FULL, A/B).
 // ZB: the latent-shortcut epilogue (VuGemmFwd.zbias) as its own
 // instantiation -- a runtime branch pushed the others to 256 VGPRs + scratch.
-// PERS (round 5, VU_TUNE_PP_PERSIST): a persistent grid (<= one block per CU)
-// walks its tiles; the next tile's first halo and first two weight slots are
-// issued before the current tile's epilogue (which stages through its own LDS
-// strips), so the per-tile prologue wait overlaps the epilogue.
-template <int BN, bool SPLIT, bool BNB, bool RELU = false, bool FULL = false, bool ZB = false, bool PERS = false>
+template <int BN, bool SPLIT, bool BNB, bool RELU = false, bool FULL = false, bool ZB = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
   constexpr int NBW = 3;                          // weight ring slots
   constexpr int WM = PP<BN>::WM, WN = PP<BN>::WN, TH = PP<BN>::TH, TW = PP<BN>::TW;
@@ -110,9 +106,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
   // pixel rows
   constexpr int SPITCH = 144;                     // staged pixel row (128 B + pad)
   constexpr int STG = 32 * SPITCH;
-  constexpr int SMEM = PERS ? MAIN + 8 * STG : MAIN;
+  constexpr int SMEM = MAIN;
   static_assert(SMEM <= 163840 && 8 * STG <= MAIN, "LDS");
-  static_assert(!(PERS && SPLIT), "persistent walk: whole-K tiles only");
   static_assert(LB0 >= 1, "DMA schedule");
   static_assert(9 % NBW == 0, "ring slot = tap % NBW");
   static_assert(TW == 32, "fragment geometry");
@@ -129,8 +124,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
   const int ksplit = SPLIT ? p.ksplit : 1;
   const int bid0 = xcd_remap(blockIdx.x, btiles * ksplit);
   const int kidx = SPLIT ? bid0 / btiles : 0;
-  // the tile this block computes (mt, img, y0, x0, n0: epilogue) and the one
-  // its DMA streams (d*: the same, or -- PERS, during the epilogue -- the next)
+  // the tile this block computes: mt, img, y0, x0, n0 for the epilogue, d* for the DMA
+  // (the same tile, computed before the prologue; folding the two sets moved scalar code)
   int mt, img, y0, x0, n0, dimg, dy0, dx0, dn0;
   auto tile_coords = [&](int b, int& m_, int& im_, int& y_, int& x_, int& n_) {
     m_ = b / ntiles;
@@ -141,7 +136,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
     x_ = (tr - (tr / tx_n) * tx_n) * TW;
     n_ = nt_ * BN;
   };
-  int cur = SPLIT ? bid0 - kidx * btiles : bid0;
+  const int cur = SPLIT ? bid0 - kidx * btiles : bid0;
   {
     int mdum;
     tile_coords(cur, mdum, dimg, dy0, dx0, dn0);
@@ -239,8 +234,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
     wstage(cbeg, 0, 0, 0, LB0);
     wstage(cbeg, 1, 1, 0, LB0);
   }
-  int kt = 0;  // PERS: tiles walked
-  for (;;) {
   tile_coords(cur, mt, img, y0, x0, n0);
   f32x4 acc[8][4];
 #pragma unroll
@@ -347,25 +340,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
     hb ^= 1;
   }
   if (!grp) pp_barrier();  // re-align the halves
-  // PERS: every wave is past its last fragment read -- the next tile's first
-  // halo (buffer 0) and weight slots 0, 1 stream in during this epilogue
-  bool more = false;
-  if constexpr (PERS) {
-    ++kt;
-    const int vb = (int)blockIdx.x + kt * (int)gridDim.x;
-    more = vb < btiles;
-    if (more) {
-      cur = xcd_remap(vb, btiles);
-      int mdum;
-      tile_coords(cur, mdum, dimg, dy0, dx0, dn0);
-      if (grp) {
-        halo_chunk(cbeg, 0);
-      } else {
-        wstage(cbeg, 0, 0, 0, LB0);
-        wstage(cbeg, 1, 1, 0, LB0);
-      }
-    }
-  }
 
   // ---- epilogue -------------------------------------------------------------
   // acc[i][j][r]: pixel wm*128 + i*16 + (lane&15), channel n0 + cbase + j*16 + r
@@ -504,15 +478,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
   // vmcnt(0), i.e. for the acknowledgement of the statistics stores just
   // issued (measured: the 17 forward layers 2.65 ms with statistics against
   // 2.44 ms without)
-  if constexpr (!PERS) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    pp_barrier();
-  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  pp_barrier();
   // fragments 2h and 2h+1 are the 32 pixels of tile row wm*4 + h
   bf16_t* const orow0 = reinterpret_cast<bf16_t*>(ep->out) + ep->out_coff + n0 + wn * 64 +
                         (((int64_t)img * H + y0 + wm * 4) * W + x0) * ep->out_stride;
   const int64_t orow_y = (int64_t)W * ep->out_stride;
-  char* const stg = smem + (PERS ? MAIN : 0) + wid * STG;
+  char* const stg = smem + wid * STG;
 #pragma unroll
   for (int h = 0; h < 4; ++h) {
 #pragma unroll
@@ -591,8 +563,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
       *reinterpret_cast<f32x4*>(pr + ep->ncol + 4) = f32x4{bs1[4], bs1[5], bs1[6], bs1[7]};
     }
   }
-  if (!more) break;
-  }  // tile walk (one pass unless PERS)
 }
 
 // split-K epilogue: out = round(sum_k slab[k] + bias) (+ out if accumulate),
@@ -866,9 +836,8 @@ Plan plan(const VuGemmFwd& p) {
 template <int BN>
 int launch(const VuGemmFwd& p, int ks, hipStream_t st) {
   const VuGather& g = p.a;
-  // VU_TUNE_PP_FULL: one phase per step (conv3x3_pp_kernel FULL; 0 = two halves);
-  // VU_TUNE_PP_PERSIST: persistent tile walk for 128/256-column tiles (PERS)
-  const int pp_full = tune(VU_TUNE_PP_FULL), pp_persist = tune(VU_TUNE_PP_PERSIST);
+  // VU_TUNE_PP_FULL: one phase per step (conv3x3_pp_kernel FULL; 0 = two halves)
+  const int pp_full = tune(VU_TUNE_PP_FULL);
   const int64_t mt = (int64_t)g.N * (g.H / PP<BN>::TH) * (g.W / PP<BN>::TW);
   const int64_t tiles = mt * (p.ncol / BN);
   if (ks <= 1) {
@@ -894,12 +863,6 @@ int launch(const VuGemmFwd& p, int ks, hipStream_t st) {
     }
     else if (p.relu)
       hipLaunchKernelGGL((conv3x3_pp_kernel<BN, false, false, true>), dim3((unsigned)tiles), dim3(512), 0, st, q);
-    else if (BN != 64 && pp_full && (pp_persist >= 2 || (pp_persist == 1 && tiles > cu_count()))) {
-      // persistent walk: one block per CU (pp_persist >= 2: the grid capped at that many blocks, tests)
-      const int64_t grid = pp_persist >= 2 ? (tiles < pp_persist ? tiles : pp_persist) : cu_count();
-      hipLaunchKernelGGL((conv3x3_pp_kernel<BN, false, false, false, BN != 64, false, BN != 64>),
-                         dim3((unsigned)grid), dim3(512), 0, st, q);
-    }
     else if (BN != 64 && pp_full)  // (BN = 64 FULL spills 11 VGPRs: up4.1 fwd 341 -> 389 us, profiles/r6z_ab_pp64_full.txt)
       hipLaunchKernelGGL((conv3x3_pp_kernel<BN, false, false, false, BN != 64>), dim3((unsigned)tiles), dim3(512), 0,
                          st, q);

@@ -45,8 +45,6 @@ constexpr Key kKeys[] = {
     {VU_TUNE_PP_FULL, 1, RAW},
     {VU_TUNE_W2_BIG, 0, RAW},
     {VU_TUNE_V6_XM, 0, RANGE, 0, 5, 1},
-    {VU_TUNE_PP_PERSIST, 0, RAW},
-    {VU_TUNE_BN_ONEPASS, 0, FLAG},
     {VU_TUNE_UNSAFE, 0, FLAG},
     {VU_TUNE_V6_STAG, 1, FLAG},
 };

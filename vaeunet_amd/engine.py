@@ -388,17 +388,20 @@ def bias_grad(dy, b, M, window=None, bn=None):
 # ----------------------------------------------------------------------------
 # BatchNorm2d: stats from the GEMM epilogue -> (scale, shift, mean, invstd)
 # ----------------------------------------------------------------------------
+def bn_running_args(bn):
+    """(running_mean, running_var, num_batches_tracked, momentum) of a
+    train-mode BatchNorm for the finalize kernels: None / 0.0 when it tracks no
+    running statistics."""
+    if not (bn.track_running_stats and bn.running_mean is not None):
+        return None, None, None, 0.0
+    return bn.running_mean, bn.running_var, bn.num_batches_tracked, 0.1 if bn.momentum is None else bn.momentum
+
+
 def bn_coef(bn, st, C_):
     if bn.training:
         if st is None:
             raise RuntimeError("train-mode BatchNorm needs GEMM statistics")
-        mom = 0.1 if bn.momentum is None else bn.momentum
-        track = bn.track_running_stats and bn.running_mean is not None
-        return K.bn_finalize(st, C_, bn.weight, bn.bias,
-                             bn.running_mean if track else None,
-                             bn.running_var if track else None,
-                             bn.num_batches_tracked if track else None, mom if track else 0.0,
-                             bn.eps)
+        return K.bn_finalize(st, C_, bn.weight, bn.bias, *bn_running_args(bn), bn.eps)
     return K.bn_eval(C_, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
 
 
@@ -416,11 +419,7 @@ def bn_fwd_apply(bn, st, y, a, relu, M, res=None, rcoef=None):
     (kernels.bn_forward_fused); otherwise finalize (bn_coef) + the apply."""
     C_ = y.shape[1]
     if FUSED_BN_FWD and bn.training and st is not None:
-        mom = 0.1 if bn.momentum is None else bn.momentum
-        track = bn.track_running_stats and bn.running_mean is not None
-        coef = K.bn_forward_fused(st, C_, bn.weight, bn.bias, bn.running_mean if track else None,
-                                  bn.running_var if track else None,
-                                  bn.num_batches_tracked if track else None, mom if track else 0.0, bn.eps,
+        coef = K.bn_forward_fused(st, C_, bn.weight, bn.bias, *bn_running_args(bn), bn.eps,
                                   y, a, relu, M.d, res=res, rcoef=rcoef)
         if coef is not None:
             return coef
@@ -446,56 +445,27 @@ def bn_grad_sinks(bn):
     return gw, gb, accw or accb
 
 
-class PoolGrad:
-    """The gradient of a BN(+ReLU) activation that fed a 2x2 max-pool (and a
-    skip connection), kept unmaterialised: dp = gradient of the pooled output,
-    add = skip gradient (or None), act = the stored activation (fallback).
-    bn_bwd runs the BN backward straight from it (vu_bn_bwd_pool)."""
-
-    def __init__(self, dp, add, act):
-        self.dp, self.add, self.act = dp, add, act
-
-    def materialize(self, M):
-        dx = torch.empty_like(self.act)
-        K.maxpool_bwd(self.act, self.dp, dx, self.add, M.d)
-        return dx
-
-
-# BatchNorm backward through the following max-pool from (pooled gradient,
-# skip gradient, BN input) instead of the materialised pool-input gradient:
-# 5.5 instead of 8.25 full-size passes per pooled layer, but every pass
-# recomputes the activation, its argmax and the pool-input gradient per
-# window (~2x the VALU work per element of the three kernels it replaces).
-# Measured SLOWER (same-box A/B, profiles/r4af_ab_pool_bn_bwd.log: UNet
-# 523.3 -> 500.0 img/s; the two passes 154 + 190 us per launch on average):
-# these streams are VALU-bound once they compute ~25 operations per element.
-# Off by default; module-level switch for A/B runs (tested either way).
-POOL_BN_BWD = False
+def bn_bwd_finish(x, coef, bn, part):
+    """The fp64 finish of a BatchNorm backward whose first reduction stage
+    (part, a BnbPart) a producing kernel emitted: dgamma / dbeta into the grad
+    sinks; returns the apply coefficients k."""
+    gw, gb, acc = bn_grad_sinks(bn)
+    return K.bn_backward_finish(part, x, coef, bn.weight, gw, gb, acc, train=bn.training)
 
 
 def bn_bwd(dy, x, coef, bn, relu, M, dx=None, part=None, zrs=None):
     """BatchNorm2d(+ReLU) backward.  Train mode differentiates through the
     batch statistics; eval mode (running statistics, constants) gives
     dx = gamma*invstd*dz and the same dgamma/dbeta sums.  part: the first
-    reduction stage, already emitted by the GEMM that produced dy.  dy may be
-    a PoolGrad (the activation fed a 2x2 max-pool).  zrs: a latent shortcut's
-    K.ZbiasRegions, filled by the apply pass when it serves."""
-    gw, gb, acc = bn_grad_sinks(bn)
+    reduction stage, already emitted by the GEMM that produced dy.  zrs: a
+    latent shortcut's K.ZbiasRegions, filled by the apply pass when it serves."""
     if dx is None:
         dx = torch.empty_like(x)
-    if isinstance(dy, PoolGrad):
-        add = dy.add
-        N, Cc, H, W = x.shape
-        if POOL_BN_BWD and K.query("vu_bn_bwd_pool_supported", H, W, Cc, K.pstride(x), K.pstride(dy.dp),
-                                   K.pstride(add) if add is not None else 8, K.pstride(dx)):
-            K.bn_backward_pool(dy.dp, add, x, coef, bn.weight, relu, gw, gb, acc, dx, K.dcode(x.dtype),
-                               train=bn.training)
-            return dx
-        dy = dy.materialize(M)
     if part is not None and part.x is x:
-        K.bn_backward_part(part, dy, x, coef, bn.weight, relu, gw, gb, acc, dx, K.dcode(x.dtype),
-                           train=bn.training, zrs=zrs)
+        k = bn_bwd_finish(x, coef, bn, part)
+        K.bn_backward_apply(dy, x, coef, k, relu, dx, K.dcode(x.dtype), zrs)
     else:
+        gw, gb, acc = bn_grad_sinks(bn)
         K.bn_backward(dy, x, coef, bn.weight, relu, gw, gb, acc, dx, K.dcode(x.dtype),
                       train=bn.training, fused=FUSED_BN_BWD, zrs=zrs)
     return dx
@@ -506,16 +476,13 @@ def bn_bwd_pair(dy, a, b, M):
     a / b = (x, coef, bn, BnbPart): both fp64 finishes, then one apply pass
     that reads dy once (vu_bn_bwd_apply2; the attention gate's W_g / W_x
     BatchNorms, round 6).  Returns (dx_a, dx_b)."""
-    outs, ks = [], []
-    for x, coef, bn, part in (a, b):
-        gw, gb, acc = bn_grad_sinks(bn)
-        ks.append(K.bn_backward_finish(part, x, coef, bn.weight, gw, gb, acc, train=bn.training))
-        outs.append(torch.empty_like(x))
+    ka, kb = bn_bwd_finish(*a), bn_bwd_finish(*b)
     (xa, ca, _, _), (xb, cb, _, _) = a, b
-    if not K.bn_backward_apply2(dy, xa, ca, ks[0], outs[0], xb, cb, ks[1], outs[1], K.dcode(xa.dtype)):
-        K._apply(dy, xa, ca, ks[0], False, outs[0], K.dcode(xa.dtype), None)
-        K._apply(dy, xb, cb, ks[1], False, outs[1], K.dcode(xb.dtype), None)
-    return outs[0], outs[1]
+    dxa, dxb = torch.empty_like(xa), torch.empty_like(xb)
+    if not K.bn_backward_apply2(dy, xa, ca, ka, dxa, xb, cb, kb, dxb, K.dcode(xa.dtype)):
+        K.bn_backward_apply(dy, xa, ca, ka, False, dxa, K.dcode(xa.dtype))
+        K.bn_backward_apply(dy, xb, cb, kb, False, dxb, K.dcode(xb.dtype))
+    return dxa, dxb
 
 
 # ----------------------------------------------------------------------------
@@ -598,7 +565,7 @@ def _image_wgrad_kernel_serves(M, srcs, conv, shortcut, da, y):
 
 
 def _image_wgrad_bn_serves(M, srcs, conv, bn, y, da, need_dsrc, da_part, shortcut):
-    if need_dsrc or isinstance(da, PoolGrad) or (da_part is not None and da_part.x is not y):
+    if need_dsrc or (da_part is not None and da_part.x is not y):
         return False
     N, Cc, H, W = y.shape
     # small tensors without epilogue partials take vu_bn_bwd_fused, which keeps
@@ -610,10 +577,10 @@ def _image_wgrad_bn_serves(M, srcs, conv, bn, y, da, need_dsrc, da_part, shortcu
 
 
 def _image_wgrad_bn(M, srcs, conv, bn, y, coef, da, cvalid, da_part):
-    gw, gb, acc = bn_grad_sinks(bn)
     if da_part is not None:
-        k = K.bn_backward_finish(da_part, y, coef, bn.weight, gw, gb, acc, train=bn.training)
+        k = bn_bwd_finish(y, coef, bn, da_part)
     else:
+        gw, gb, acc = bn_grad_sinks(bn)
         k = K.bn_backward_reduce(da, y, coef, bn.weight, True, gw, gb, acc, M.d, train=bn.training)
 
     def wg():
@@ -716,16 +683,16 @@ def down_fwd(M, mod, x, pend=None, defer=False):
 
 
 def down_bwd(M, mod, saved, dout, add=None):
-    """d(loss)/d(this Down's input) as a PoolGrad (the pooled gradient + add,
-    the skip gradient): the producing DoubleConv's BN2 backward reads it
-    through the pool (round 4).  (Round 2: a max-pool backward carrying that
-    BN's backward reduction streamed five tensors and measured slower than the
-    two passes it replaced: DESIGN.md §4.2.)"""
+    """d(loss)/d(this Down's input): the max-pool backward of the pooled
+    gradient plus add, the skip gradient.  (A max-pool backward carrying the
+    producing BN's backward reduction, and that BN's backward read through the
+    pool, both measured slower than these separate passes: DESIGN.md §4.2.)"""
     x, sdc = saved
     seq = mod.maxpool_conv[1].double_conv
     dxp = double_conv_bwd(M, seq, sdc, dout, True)
-    # unmaterialised: the producing DoubleConv's BN2 backward takes it (bn_bwd)
-    return PoolGrad(dxp, add, x)
+    dx = torch.empty_like(x)
+    K.maxpool_bwd(x, dxp, dx, add, M.d)
+    return dx
 
 
 # ----------------------------------------------------------------------------
@@ -841,10 +808,7 @@ def attention_bwd(M, att, saved, dout, dg_out, dg_acc):
                K.ptr(gbp), 1 if accp else 0, K.ptr(ws), M.d, K.stream())
     if tail:
         # both fp64 finishes (bn_bwd_pair's), then the one pass
-        ks = []
-        for u_, c_, bn_, part in ((ug, cg, bng, pg), (ux, cx, bnx, px)):
-            gw_, gb_, acc_ = bn_grad_sinks(bn_)
-            ks.append(K.bn_backward_finish(part, u_, c_, bn_.weight, gw_, gb_, acc_, train=bn_.training))
+        ks = [bn_bwd_finish(ug, cg, bng, pg), bn_bwd_finish(ux, cx, bnx, px)]
         dug, dux = torch.empty_like(ug), torch.empty_like(ux)
         wdg, wdx = w1x1_dgrad(wg.weight, M.d), w1x1_dgrad(wx.weight, M.d)
         dst, coff = dg_out

@@ -559,9 +559,10 @@ class ZbiasRegions:
         self.rs, self.ready = rs, False
 
 
-def _apply(dy, x, coef, k, relu, dx, dtype, zrs):
-    """The BN backward apply pass; with zrs (a ZbiasRegions) the fused variant
-    that also takes the shortcut's region partials of dx, when it serves."""
+def bn_backward_apply(dy, x, coef, k, relu, dx, dtype, zrs=None):
+    """The BN backward apply pass (k from bn_backward_reduce or
+    bn_backward_finish); with zrs (a ZbiasRegions) the fused variant that also
+    takes the shortcut's region partials of dx, when it serves."""
     N, Cc, H, W = x.shape
     if zrs is not None and query("vu_bn_bwd_apply_zrs_ok", H, W, Cc, pstride(dy), pstride(x), pstride(dx)):
         call("vu_bn_bwd_apply_zrs", ptr(dy), pstride(dy), ptr(x), pstride(x), N, H, W, Cc, ptr(coef[0]),
@@ -582,58 +583,22 @@ def bn_backward(dy, x, coef, gamma, relu, dgamma, dbeta, acc, dx, dtype, train=T
     only)."""
     N, Cc, H, W = x.shape
     P = N * H * W
-    dev = x.device
-    ws = torch.empty(query("vu_reduce_workspace_bytes", P, Cc) // 4 + 1, dtype=torch.float32,
-                     device=dev)
     # (the small-tensor two-launch path keeps its own, more accurate fp64
     # reduction: a zrs is then left unfilled and the region pass runs)
     if fused and query("vu_bn_bwd_fused_supported", P, Cc, pstride(dy), pstride(x), pstride(dx)):
+        ws = torch.empty(query("vu_reduce_workspace_bytes", P, Cc) // 4 + 1, dtype=torch.float32, device=x.device)
         call("vu_bn_bwd_fused", ptr(dy), pstride(dy), ptr(x), pstride(x), P, Cc, ptr(coef[0]), ptr(coef[1]),
              ptr(coef[2]), ptr(coef[3]), ptr(gamma), 1 if relu else 0, 1 if train else 0, ptr(dgamma), ptr(dbeta),
              1 if acc else 0, ptr(dx), pstride(dx), ptr(ws), dtype, stream())
         return dx
-    k = torch.empty((3, Cc), dtype=torch.float32, device=dev)
-    call("vu_bn_bwd_reduce", ptr(dy), pstride(dy), ptr(x), pstride(x), P, Cc, ptr(coef[0]),
-         ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), ptr(gamma), 1 if relu else 0,
-         1 if train else 0, ptr(dgamma), ptr(dbeta), 1 if acc else 0, ptr(k), ptr(ws), dtype,
-         stream())
-    _apply(dy, x, coef, k, relu, dx, dtype, zrs)
-    return dx
-
-
-def bn_backward_pool(dp, add, y, coef, gamma, relu, dgamma, dbeta, acc, dx, dtype, train=True):
-    """BatchNorm(+ReLU) backward through the 2x2 max-pool that follows it
-    (vu_bn_bwd_pool): dp the pooled output's gradient, add the skip gradient
-    of the activation (or None); dx = the gradient of y (the BN input)."""
-    N, Cc, H, W = y.shape
-    P = N * H * W
-    ws = workspace_f32(query("vu_reduce_workspace_bytes", P, Cc), y.device)
-    k = torch.empty((3, Cc), dtype=torch.float32, device=y.device)
-    call("vu_bn_bwd_pool", ptr(y), pstride(y), ptr(dp), pstride(dp), ptr(add), pstride(add) if add is not None else 0,
-         N, H, W, Cc, ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), ptr(gamma), 1 if relu else 0,
-         1 if train else 0, ptr(dgamma), ptr(dbeta), 1 if acc else 0, ptr(k), ptr(ws), ptr(dx), pstride(dx),
-         dtype, stream())
-    return dx
-
-
-def bn_backward_part(part, dy, x, coef, gamma, relu, dgamma, dbeta, acc, dx, dtype, train=True, zrs=None):
-    """bn_backward with the first reduction stage done by the producing GEMM's
-    epilogue (a BnbPart): the fp64 finish, then the apply pass (zrs: as
-    bn_backward)."""
-    N, Cc, H, W = x.shape
-    P = N * H * W
-    k = torch.empty((3, Cc), dtype=torch.float32, device=x.device)
-    nb = query("vu_bn_bwd_finish_workspace_bytes", part.nblk, Cc)
-    ws = workspace_f32(nb, x.device) if nb > 0 else None
-    call("vu_bn_bwd_finish", ptr(part.part), part.nblk, P, Cc, ptr(gamma), ptr(coef[3]), 1 if train else 0,
-         ptr(dgamma), ptr(dbeta), 1 if acc else 0, ptr(k), ptr(ws), stream())
-    _apply(dy, x, coef, k, relu, dx, dtype, zrs)
+    k = bn_backward_reduce(dy, x, coef, gamma, relu, dgamma, dbeta, acc, dtype, train)
+    bn_backward_apply(dy, x, coef, k, relu, dx, dtype, zrs)
     return dx
 
 
 def bn_backward_finish(part, x, coef, gamma, dgamma, dbeta, acc, train=True):
     """The fp64 finish of a BnbPart: dgamma / dbeta written (or added) and the
-    apply coefficients k (3 x C) returned -- bn_backward_part without its apply."""
+    apply coefficients k (3 x C) returned (for bn_backward_apply)."""
     N, Cc, H, W = x.shape
     k = torch.empty((3, Cc), dtype=torch.float32, device=x.device)
     nb = query("vu_bn_bwd_finish_workspace_bytes", part.nblk, Cc)

@@ -93,7 +93,7 @@ class Down(nn.Module):
 
         def bwd(state, dout):
             # a standalone Down has no producing BN to hand the pooled gradient to
-            return (E.from_act(E.down_bwd(M, self, state, act_grad(M, dout)).materialize(M), x),)
+            return (E.from_act(E.down_bwd(M, self, state, act_grad(M, dout)), x),)
         return run_block(self, fwd, bwd, (x,))
 
 
