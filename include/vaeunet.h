@@ -1092,6 +1092,59 @@ int vu_augment_patch(const float* img, const float* msk, int B, int H, int W,
                      uint32_t offset, float* out_img, float* out_msk,
                      void* stream);
 
+/* CLAHE and separable blur of an image batch img [B][H][W][3] (NHWC fp32) ->
+ * out of the same shape, no aliasing (this project's own
+ * definitions, unpinned against albumentations / OpenCV).  In the patch
+ * loader both run ahead of vu_augment_patch: CLAHE, then blur, then the warp.
+ *
+ * CLAHE, clip [B] fp32 (device), TY x TX tiles, 256 bins:
+ *   q(v)  = (int)(fminf(fmaxf(v, 0), 1) * 255.0f + 0.5f), the product and the
+ *           sum rounded separately in fp32 (no fma); a NaN gives 0
+ *   Y8    = (77 q(r) + 150 q(g) + 29 q(b) + 128) >> 8                in 0..255
+ *   tiles   tile t of an axis of n pixels in T tiles is [s(t), s(t+1)), s(t) =
+ *           floor(t n / T), no padding; 1 <= T <= 16 and T <= n; the tile of
+ *           row y is floor(((y + 1) T - 1) / n); area A per tile
+ *   limit   t = clip * (float)A * (1.0f / 256) in fp32; lim = A where t >= A,
+ *           else max(1, (int)t)
+ *   clip    h = histogram of Y8 over the tile; E = sum max(h - lim, 0);
+ *           h = min(h, lim) + E / 256; r = E % 256; if r > 0: step =
+ *           max(256 / r, 1) and bin i gains 1 where i % step == 0 and
+ *           i / step < r (OpenCV's order; the total stays A)
+ *   lut[i] = (cdf[i] * 255 + A / 2) / A in 64-bit integers, uint8; monotone,
+ *           lut[255] = 255.  vu_clahe_luts writes luts [B][TY][TX][256].
+ *   blend   C(t) = s(t) + s(t+1) - 1 is twice the centre of tile t.  For row y,
+ *           P = 2 y: t1 = the last tile with C <= P, t2 = t1 + 1, wy =
+ *           (float)(P - C(t1)) / (float)(C(t2) - C(t1)); before the first
+ *           centre or from the last one on, t1 = t2 = the edge tile and wy = 0.
+ *           Columns likewise.  With lerp(a, b, t) = a + t (b - a) and the four
+ *           LUT values at bin Y8 (L11 = tile (ty1, tx1), L12 = (ty1, tx2), ...):
+ *           Y' = lerp(lerp(L11, L12, wx), lerp(L21, L22, wx), wy)
+ *   out_c = clamp(v_c + (Y' - Y8) * (1.0f / 255), 0, 1)          (a NaN gives 0)
+ * A sample whose clip is not > 0 (0, negative, NaN) is off: vu_clahe_apply
+ * copies it bitwise and vu_clahe_luts writes the identity table lut[i] = i.
+ *
+ * Blur, table [B][9] fp32 (device) = r, w_0 .. w_7 per sample; the kernel uses
+ * r = (int)clamp(table[0], 0, 7) (a NaN gives 0) and w_0 .. w_r:
+ *   pass    acc = w_0 x; acc = fmaf(w_k, x[-k] + x[+k], acc) for k = 1 .. r,
+ *           ascending; the horizontal pass first, the vertical pass on its
+ *           result (which never reaches memory)
+ *   border  reflect101: the tap index folded with period 2 (size - 1), size 1
+ *           gives index 0 (the rule of vu_augment_patch)
+ * r = 0 with w_0 = 1 returns the input bitwise.  A pixel's result depends on
+ * its sample and position only, not on B or the launch geometry.
+ *
+ * hipErrorInvalidValue, nothing launched: a negative size, TY or TX outside
+ * 1..16, then (B > 0) a null pointer, B > 65535, H or W > 32768, TY > H or
+ * TX > W.  B == 0 (for vu_blur_sep also H or W == 0) returns 0, nothing
+ * launched. */
+int vu_clahe_luts(const float* img, int B, int H, int W, const float* clip,
+                  int TY, int TX, uint8_t* luts, void* stream);
+int vu_clahe_apply(const float* img, int B, int H, int W, const float* clip,
+                   int TY, int TX, const uint8_t* luts, float* out,
+                   void* stream);
+int vu_blur_sep(const float* img, int B, int H, int W, const float* table,
+                float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

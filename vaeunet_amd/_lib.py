@@ -231,6 +231,9 @@ _SIGS = {
     "vu_gather_affine": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
     "vu_patch_stats": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p]),
     "vu_augment_patch": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, C.c_uint64, C.c_uint32, _p, _p, _p]),
+    "vu_clahe_luts": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p]),
+    "vu_clahe_apply": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
+    "vu_blur_sep": (_i, [_p, _i, _i, _i, _p, _p, _p]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@
 // offset, sample, pixel): Philox4x32-10, counter = (pixel lo, pixel hi,
 // sample, offset), key = seed; it does not depend on B or the tile shape.
 #include "common.h"
+#include "reflect.h"
 #include "../../include/vaeunet.h"
 
 namespace {
@@ -33,16 +34,6 @@ constexpr int AUG_NPARAM = 20;
 constexpr float AUG_COORD_MAX = 1048576.f;   // 2^20
 
 enum { AUG_BORDER_CONSTANT = 0, AUG_BORDER_REFLECT101 = 1 };
-
-// index folded with period 2 (size - 1): ... 2 1 | 0 1 2 ... n-1 | n-2 ...
-VU_DEV int reflect101(int i, int size) {
-  if ((unsigned)i < (unsigned)size) return i;
-  if (size == 1) return 0;
-  const int p = 2 * (size - 1);
-  int m = i % p;
-  if (m < 0) m += p;
-  return m < size ? m : p - m;
-}
 
 // tap index and validity under the launch's border mode
 template <int BORDER>

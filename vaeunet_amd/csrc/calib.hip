@@ -24,6 +24,7 @@
 // tools/calib_bench.py measured fastest on a skewed map (DESIGN.md 4.6;
 // -DVU_CALIB_PEEL=0 / 2 build the other forms of that A/B).
 #include "common.h"
+#include "lds_hist.h"
 #include "../../include/vaeunet.h"
 
 #ifndef VU_CALIB_PEEL
@@ -74,24 +75,6 @@ VU_DEV void truth4(const int64_t* p, bool (&t)[4]) {
   for (int j = 0; j < 4; ++j) t[j] = (float)e[j] > 0.5f;
 }
 
-// h[idx] += 1 for every lane with pend set.  Called by whole waves (pend is
-// false on lanes without a pixel).
-VU_DEV void hist_add(uint32_t* h, int idx, bool pend) {
-#pragma unroll
-  for (int r = 0; r < VU_CALIB_PEEL; ++r) {
-    if (pend) {
-      const int first = __builtin_amdgcn_readfirstlane(idx);
-      const bool same = idx == first;
-      const u64 mask = __ballot(same);
-      if (same) {
-        if ((int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicAdd(&h[first], (uint32_t)__popcll(mask));
-        pend = false;
-      }
-    }
-  }
-  if (pend) atomicAdd(&h[idx], 1u);
-}
-
 // min((int)v, bins - 1) for v >= 0; the clamp ahead of the conversion keeps it
 // defined for huge v and does not change the result for the others
 VU_DEV int bin_of(float v, int bins) { return min((int)fminf(v, (float)bins), bins - 1); }
@@ -109,13 +92,13 @@ VU_DEV void pixel(bool valid, float p, bool t, float u, int nb, float uscale, ui
   const float pc = ok ? fminf(fmaxf(p, 0.f), 1.f) : 0.f;
   const int cb = bin_of(pc * (float)nb, nb);
   const int rb = bin_of(pc * (float)R, R);
-  hist_add(hc, cb * 2 + (int)t, ok);
-  hist_add(hr, rb * 2 + (int)t, ok);
+  hist_add<VU_CALIB_PEEL>(hc, cb * 2 + (int)t, ok);
+  hist_add<VU_CALIB_PEEL>(hr, rb * 2 + (int)t, ok);
   if (HAS_U) {
     const bool uok = ok && !(u != u);
     a.inv_u += ok && !uok;
     const int ub = bin_of(fmaxf(uok ? u : 0.f, 0.f) * uscale, R);
-    hist_add(hu, ub * 2 + (int)((pc > 0.5f) != t), uok);
+    hist_add<VU_CALIB_PEEL>(hu, ub * 2 + (int)((pc > 0.5f) != t), uok);
   }
   if (ok) {
     const double q = (double)pc, d = q - (t ? 1.0 : 0.0);

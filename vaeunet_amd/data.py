@@ -36,7 +36,13 @@ contrast / saturation / hue as one colour matrix, Gaussian noise (Philox) and
 the clip to [0, 1].  The reference takes these from albumentations
 (:121-178), which is absent here, so the transforms are defined in §4.8 and
 their ranges are ``TrainAugment``'s arguments: unpinned vs the reference.
-CLAHE and blur (a histogram pass, a neighbourhood pass) stay out of scope.
+CLAHE (``clahe``: per-tile histograms of an integer luma, then a per-pixel
+blend of four lookup tables) and blur (``blur``: a separable symmetric kernel
+of radius <= 7, Gaussian or box rows from ``blur_weights``) are launches of
+their own ahead of that one, so both see the un-warped patch
+and the noise stays white; ``TrainAugment(p_clahe=, p_blur=)`` draws them per
+sample.  Their definitions are this project's too; the LAB-space CLAHE and
+MedianBlur are not built.
 Normalize(mean=0, std=1) of train.py:37 is the identity.
 """
 import logging
@@ -255,6 +261,9 @@ def _flip_rot_map(P, hflip, vflip, k):
 # ----------------------------------------------------------------------------
 NPARAM = 20                       # a0..a5, gamma, M (9), o (3), sigma
 MAX_GRID_STEPS = 32
+RMAX = 7                          # largest blur radius
+NBLUR = 2 + RMAX                  # a blur row: r, w_0..w_RMAX
+MAX_TILES = 16                    # CLAHE tiles per axis
 BORDERS = {"constant": 0, "reflect101": 1}
 
 _GREY = np.array([0.299, 0.587, 0.114])
@@ -314,6 +323,41 @@ def identity_params(B):
     return p
 
 
+def blur_weights(sigma=None, box=None):
+    """One row [9] fp32 = r, w_0..w_7 of the separable blur,
+    built in float64, normalised to w_0 + 2 sum w_k = 1 and rounded to fp32.
+    ``sigma``: a Gaussian exp(-k^2 / (2 sigma^2)) with r = min(7, ceil(3 sigma));
+    taps that are 0 in fp32 are dropped, so sigma -> 0 gives the identity row
+    [0, 1, 0, ...].  ``box``: the odd width 2r + 1 <= 15 of a box filter."""
+    if (sigma is None) == (box is None):
+        raise ValueError("give exactly one of sigma and box")
+    if box is not None:
+        if int(box) != box or not 1 <= int(box) <= 2 * RMAX + 1 or int(box) % 2 == 0:
+            raise ValueError(f"box must be an odd width in [1, {2 * RMAX + 1}], got {box}")
+        r = (int(box) - 1) // 2
+        w = np.ones(r + 1)
+    else:
+        sigma = float(sigma)
+        if not (np.isfinite(sigma) and sigma >= 0):
+            raise ValueError(f"sigma must be finite and non-negative, got {sigma}")
+        r = min(RMAX, int(np.ceil(3.0 * sigma)))
+        k = np.arange(r + 1, dtype=np.float64)
+        w = np.exp(-k * k / (2.0 * sigma * sigma)) if r > 0 else np.ones(1)
+    w = (w / (w[0] + 2.0 * w[1:].sum())).astype(np.float32)
+    while r > 0 and w[r] == 0:
+        r -= 1
+    row = np.zeros(NBLUR, np.float32)
+    row[0], row[1:r + 2] = r, w[:r + 1]
+    return row
+
+
+def identity_blur(B):
+    """[B, 9] fp32: r = 0, w_0 = 1 for every sample."""
+    t = np.zeros((B, NBLUR), np.float32)
+    t[:, 1] = 1.0
+    return t
+
+
 class TrainAugment:
     """Probabilities and ranges of the device-side training transform
     (``PatchCache(augment=TrainAugment(...))``).  The defaults are this
@@ -328,12 +372,16 @@ class TrainAugment:
     photometry p_gamma with gamma_range; p_colour with brightness_limit,
                contrast_limit, saturation_limit, hue_limit (turns);
                p_noise with noise_sigma range
-    border     'reflect101' or 'constant'"""
+    border     'reflect101' or 'constant'
+    filters    (ahead of the warp, image only; off by default)
+               p_clahe with the clahe_clip range and clahe_tiles (rows,
+               columns); p_blur with the blur_sigma range of a Gaussian"""
 
     def __init__(self, p_hflip=0.5, p_vflip=0.5, p_rot90=0.5, p_affine=0.5, rotate_limit=15.0, scale_limit=0.1,
                  shift_limit=0.0625, p_grid=0.3, grid_steps=5, grid_limit=0.3, p_gamma=0.3, gamma_range=(0.8, 1.25),
                  p_colour=0.5, brightness_limit=0.2, contrast_limit=0.2, saturation_limit=0.2, hue_limit=0.02,
-                 p_noise=0.3, noise_sigma=(0.005, 0.03), border="reflect101"):
+                 p_noise=0.3, noise_sigma=(0.005, 0.03), border="reflect101", p_clahe=0.0, clahe_clip=(1.0, 4.0),
+                 clahe_tiles=(8, 8), p_blur=0.0, blur_sigma=(0.5, 1.5)):
         if border not in BORDERS:
             raise ValueError(f"border must be one of {sorted(BORDERS)}, got {border!r}")
         if not 1 <= int(grid_steps) <= MAX_GRID_STEPS:
@@ -352,6 +400,11 @@ class TrainAugment:
         self.saturation_limit, self.hue_limit = saturation_limit, hue_limit
         self.p_noise, self.noise_sigma = p_noise, tuple(noise_sigma)
         self.border = border
+        if not (0 < clahe_clip[0] <= clahe_clip[1] < np.inf) or not (0 <= blur_sigma[0] <= blur_sigma[1] < np.inf):
+            raise ValueError("clahe_clip must be positive and blur_sigma non-negative, both finite and ascending")
+        self.clahe_tiles = _check_tiles(clahe_tiles)
+        self.p_clahe, self.clahe_clip = p_clahe, tuple(clahe_clip)
+        self.p_blur, self.blur_sigma = p_blur, tuple(blur_sigma)
 
     def _knots(self, size, S, rng):
         w = 1.0 + rng.uniform(-self.grid_limit, self.grid_limit, S)
@@ -394,6 +447,19 @@ class TrainAugment:
                 params[b, 19] = rng.uniform(*self.noise_sigma)
         return params, gx, gy
 
+    def draw_filters(self, B, rng):
+        """Host arrays (clip [B], blur table [B, 9]) fp32 for one batch: a sample
+        whose coin fails gets clip 0 (CLAHE off) / the identity blur row.
+        PatchCache calls it after ``draw``, and only when p_clahe or p_blur
+        is positive, so ``draw``'s sequence is what it was without them."""
+        clip, table = np.zeros(B, np.float32), identity_blur(B)
+        for b in range(B):
+            if rng.random() < self.p_clahe:
+                clip[b] = rng.uniform(*self.clahe_clip)
+            if rng.random() < self.p_blur:
+                table[b] = blur_weights(sigma=rng.uniform(*self.blur_sigma))
+        return clip, table
+
 
 def _check_augment_args(img, msk, params, gx, gy, seed, offset, border):
     """Host validation of one augmentation call; returns (params, gx, gy) as
@@ -427,6 +493,99 @@ def _check_augment_args(img, msk, params, gx, gy, seed, offset, border):
     return params, gx, gy
 
 
+def _check_tiles(tiles):
+    """(TY, TX) as ints in [1, 16]"""
+    try:
+        ty, tx = tiles
+        ok = int(ty) == ty and int(tx) == tx and 1 <= ty <= MAX_TILES and 1 <= tx <= MAX_TILES
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"tiles must be two integers (rows, columns) in [1, {MAX_TILES}], got {tiles!r}")
+    return int(ty), int(tx)
+
+
+def _check_filter_args(img, clip=None, tiles=(8, 8), table=None):
+    """Host validation of a CLAHE and / or blur call on image [B, 3, H, W];
+    returns (clip [B] or None, (TY, TX), table [B, 9] or None) as contiguous
+    fp32 numpy arrays.  Nothing here touches a device."""
+    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
+        raise ValueError(f"expected image [B, 3, H >= 1, W >= 1], got {tuple(img.shape)}")
+    if img.dtype != torch.float32:
+        raise ValueError("image must be float32")
+    B, _, H, W = img.shape
+    tiles = _check_tiles(tiles)
+    if clip is not None:
+        clip = np.asarray(clip, dtype=np.float32)
+        clip = np.ascontiguousarray(np.broadcast_to(clip, (B,)) if clip.ndim == 0 else clip)
+        if clip.shape != (B,):
+            raise ValueError(f"the clip limit must be a scalar or [{B}], got {clip.shape}")
+        if not (np.isfinite(clip) & (clip >= 0)).all():
+            raise ValueError("every clip limit must be finite and >= 0 (0 switches the sample off)")
+        if tiles[0] > H or tiles[1] > W:
+            raise ValueError(f"{tiles[0]} x {tiles[1]} tiles do not fit a {H} x {W} image")
+    if table is not None:
+        table = np.ascontiguousarray(table, dtype=np.float32)
+        if table.shape != (B, NBLUR):
+            raise ValueError(f"the blur table must be [{B}, {NBLUR}] = r, w_0..w_{RMAX}, got {table.shape}")
+        if not np.isfinite(table).all():
+            raise ValueError("the blur table holds a non-finite value")
+        r = table[:, 0]
+        if not ((r == np.round(r)) & (r >= 0) & (r <= RMAX)).all():
+            raise ValueError(f"every blur radius must be an integer in [0, {RMAX}]")
+    return clip, tiles, table
+
+
+def _launch_clahe(img, dclip, tiles):
+    """vu_clahe_luts + vu_clahe_apply on device tensors"""
+    img = img.contiguous(memory_format=CL)
+    B, _, H, W = img.shape
+    luts = torch.empty((B, tiles[0], tiles[1], 256), dtype=torch.uint8, device=img.device)
+    out = K.empty_act(B, 3, H, W, torch.float32, img.device)
+    with torch.cuda.device(img.device):
+        K.call("vu_clahe_luts", K.ptr(img), B, H, W, K.ptr(dclip), tiles[0], tiles[1], K.ptr(luts), K.stream())
+        K.call("vu_clahe_apply", K.ptr(img), B, H, W, K.ptr(dclip), tiles[0], tiles[1], K.ptr(luts), K.ptr(out),
+               K.stream())
+    return out
+
+
+def _launch_blur(img, dtable):
+    """The one vu_blur_sep launch on device tensors"""
+    img = img.contiguous(memory_format=CL)
+    B, _, H, W = img.shape
+    out = K.empty_act(B, 3, H, W, torch.float32, img.device)
+    with torch.cuda.device(img.device):
+        K.call("vu_blur_sep", K.ptr(img), B, H, W, K.ptr(dtable), K.ptr(out), K.stream())
+    return out
+
+
+def _need_device(img, what):
+    if img.device.type != "cuda":
+        raise RuntimeError(f"{what} runs on MI355X (HIP) devices only; got {img.device}")
+
+
+def clahe(image, clip_limit=2.0, tiles=(8, 8)):
+    """CLAHE of image [B, 3, H, W] (fp32 on the device) on an integer luma
+    (DESIGN.md §4.9): per-tile clipped histograms -> lookup tables, blended
+    per pixel, the luma change added to every channel.  ``clip_limit``: a
+    scalar or one value per sample, 0 = off (the sample comes back bitwise);
+    ``tiles`` = (rows, columns), each in 1..16 and at most the image size.
+    Returns channels_last.  Checked on the host first (ValueError)."""
+    clip, tiles, _ = _check_filter_args(image, clip=clip_limit, tiles=tiles)
+    _need_device(image, "clahe")
+    return _launch_clahe(image, torch.from_numpy(clip).to(image.device), tiles)
+
+
+def blur(image, table):
+    """Separable symmetric blur of image [B, 3, H, W] (fp32 on the device) with
+    one row r, w_0..w_7 per sample (``blur_weights``; [B, 9]), reflect101
+    border, horizontal then vertical pass in one launch.
+    Returns channels_last.  Checked on the host first (ValueError)."""
+    _, _, table = _check_filter_args(image, table=table)
+    _need_device(image, "blur")
+    return _launch_blur(image, torch.from_numpy(table).to(image.device))
+
+
 def _launch_augment(img, msk, dparams, dgx, dgy, seed, offset, border):
     """The one vu_augment_patch launch on device tensors (border: the C code)."""
     img = img.contiguous(memory_format=CL)
@@ -441,23 +600,36 @@ def _launch_augment(img, msk, dparams, dgx, dgy, seed, offset, border):
     return oimg, omsk
 
 
-def augment_patches(img, msk, params, gx, gy, seed, offset=0, border="reflect101"):
+def augment_patches(img, msk, params, gx, gy, seed, offset=0, border="reflect101", clahe_clip=None,
+                    clahe_tiles=(8, 8), blur=None):
     """Augment image [B, 3, H, W] and mask [B, Cm, H, W] (fp32 on the device) in
     ONE launch (vu_augment_patch) with the host arrays of
     ``TrainAugment.draw`` (or any of the same layout); returns (image, mask),
     channels_last on the device.  The arrays are checked here before they are
     uploaded (finite, consistent shapes, increasing knots: ValueError); the
     kernel's coordinate clamp is the second line of defence.  The noise is a
-    function of (seed, offset, sample, pixel) alone."""
+    function of (seed, offset, sample, pixel) alone.  ``clahe_clip`` (scalar or
+    [B], with ``clahe_tiles``) and ``blur`` ([B, 9]), the arrays of
+    ``TrainAugment.draw_filters``, run CLAHE and / or the blur on the image
+    ahead of that launch; their tables ride in the same
+    upload."""
     params, gx, gy = _check_augment_args(img, msk, params, gx, gy, seed, offset, border)
+    clip, tiles, table = _check_filter_args(img, clahe_clip, clahe_tiles, blur)
     if img.device.type != "cuda" or msk.device != img.device:
         raise RuntimeError(f"augment_patches runs on MI355X (HIP) devices only; got {img.device} and {msk.device}")
     B, S1 = params.shape[0], gx.shape[1]
-    host = torch.from_numpy(np.concatenate([params.reshape(-1), gx.reshape(-1), gy.reshape(-1)]))
-    dev = host.to(img.device)                    # one upload for the three tables
+    parts = [params.reshape(-1), gx.reshape(-1), gy.reshape(-1)]
+    parts += [a.reshape(-1) for a in (clip, table) if a is not None]
+    dev = torch.from_numpy(np.concatenate(parts)).to(img.device)      # one upload for every table
     n0, n1 = B * NPARAM, B * S1
+    n2 = n0 + 2 * n1
+    if clip is not None:
+        img = _launch_clahe(img, dev[n2:n2 + B], tiles)
+        n2 += B
+    if table is not None:
+        img = _launch_blur(img, dev[n2:].view(B, NBLUR))
     return _launch_augment(img, msk, dev[:n0].view(B, NPARAM), dev[n0:n0 + n1].view(B, S1),
-                           dev[n0 + n1:].view(B, S1), seed, offset, BORDERS[border])
+                           dev[n0 + n1:n0 + 2 * n1].view(B, S1), seed, offset, BORDERS[border])
 
 
 class PatchCache:
@@ -470,8 +642,10 @@ class PatchCache:
     ``TrainAugment`` for the full device-side transform (one draw and one
     launch per batch; the Philox key is ``seed``, the offset the number of
     batches augmented so far; the batch gains ``aug_params``, what
-    ``augment_patches`` needs to replay it).  All draws come from the
-    generator seeded with ``seed``."""
+    ``augment_patches`` needs to replay it; with ``p_clahe`` / ``p_blur``
+    positive the CLAHE and blur launches run first and their drawn arrays
+    join ``aug_params``).  All draws come from the generator seeded with
+    ``seed``."""
 
     def __init__(self, paths, batch_size, device="cuda", augment=False, shuffle=False, seed=0, workers=6,
                  drop_last=False):
@@ -551,6 +725,12 @@ class PatchCache:
                 params, gx, gy = self.augment.draw(img.shape[0], img.shape[2], img.shape[3], self.rng)
                 aug = {"params": params, "gx": gx, "gy": gy, "seed": self.seed & (2 ** 64 - 1),
                        "offset": self.aug_calls & 0xffffffff, "border": self.augment.border}
+                if self.augment.p_clahe > 0 or self.augment.p_blur > 0:
+                    clip, table = self.augment.draw_filters(img.shape[0], self.rng)
+                    if self.augment.p_clahe > 0:
+                        aug["clahe_clip"], aug["clahe_tiles"] = clip, self.augment.clahe_tiles
+                    if self.augment.p_blur > 0:
+                        aug["blur"] = table
                 img, msk = augment_patches(img, msk, **aug)
                 self.aug_calls += 1
                 extra["aug_params"] = aug

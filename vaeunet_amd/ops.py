@@ -34,6 +34,8 @@ Reference ops each one replaces:
                                  NLL, AUROC / AUPRC, sparsification) as one fused pass
   augment_patch                  the albumentations training transform of utils/data_loading.py:116-178 (warp,
                                  colour, noise; DESIGN.md §4.8's definitions) as one launch per batch
+  clahe / blur_separable         the CLAHE and Blur / GaussianBlur steps of that transform (DESIGN.md §4.9's
+                                 definitions; integer-luma CLAHE, separable kernel of radius <= 7)
 """
 import ctypes as C
 import types
@@ -759,7 +761,64 @@ def _(image, mask, params, gx, gy, seed, offset=0, reflect=True):
     return _cl_empty(*image.shape, image), _cl_empty(*mask.shape, mask)
 
 
+# ---- CLAHE and separable blur --------------------------------------------------------------
+def _filter_check(image, what):
+    if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] < 1 or image.shape[3] < 1:
+        raise ValueError(f"vaeunet::{what}: expected image [B, 3, H >= 1, W >= 1], got {tuple(image.shape)}")
+
+
+def _clahe_check(image, clip, tiles_y, tiles_x):
+    _filter_check(image, "clahe")
+    T = _data.MAX_TILES
+    if not (1 <= tiles_y <= min(T, image.shape[2]) and 1 <= tiles_x <= min(T, image.shape[3])):
+        raise ValueError(f"vaeunet::clahe: tiles must be in [1, {T}] and at most the image size, got {tiles_y} x "
+                         f"{tiles_x} on {tuple(image.shape[2:])}")
+    if tuple(clip.shape) != (image.shape[0],) or clip.dtype != torch.float32 or image.dtype != torch.float32:
+        raise ValueError("vaeunet::clahe: clip must be [B] and both tensors float32")
+
+
+@torch.library.custom_op(f"{_NS}::clahe", mutates_args=(), device_types="cuda")
+def clahe(image: torch.Tensor, clip: torch.Tensor, tiles_y: int = 8, tiles_x: int = 8) -> torch.Tensor:
+    """vaeunet_amd.data.clahe on a device table: image [B, 3, H, W] fp32, clip
+    [B] fp32 on the device (a value that is not > 0 switches its sample off; NOT
+    validated here, use data.clahe for host values), tiles_y x tiles_x tiles
+    (DESIGN.md §4.9).  Returns channels_last.  Not differentiable (the luma is
+    quantised to 8 bits)."""
+    _clahe_check(image, clip, tiles_y, tiles_x)
+    return _data._launch_clahe(image, clip.contiguous(), (tiles_y, tiles_x))
+
+
+@clahe.register_fake
+def _(image, clip, tiles_y=8, tiles_x=8):
+    _clahe_check(image, clip, tiles_y, tiles_x)
+    return _cl_empty(*image.shape, image)
+
+
+def _blur_check(image, table):
+    _filter_check(image, "blur_separable")
+    if tuple(table.shape) != (image.shape[0], _data.NBLUR) or table.dtype != torch.float32 \
+            or image.dtype != torch.float32:
+        raise ValueError(f"vaeunet::blur_separable: table must be [B, {_data.NBLUR}] and both tensors float32")
+
+
+@torch.library.custom_op(f"{_NS}::blur_separable", mutates_args=(), device_types="cuda")
+def blur_separable(image: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """vaeunet_amd.data.blur on a device table: image [B, 3, H, W] fp32, table
+    [B, 9] fp32 = r, w_0..w_7 per sample (data.blur_weights' rows; the kernel
+    clamps r to 0..7; NOT validated here), reflect101 border, both passes in one
+    launch.  Returns channels_last.  Not differentiable (a
+    data transform)."""
+    _blur_check(image, table)
+    return _data._launch_blur(image, table.contiguous())
+
+
+@blur_separable.register_fake
+def _(image, table):
+    _blur_check(image, table)
+    return _cl_empty(*image.shape, image)
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
-       "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch")
+       "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch", "clahe", "blur_separable")
