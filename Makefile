@@ -8,7 +8,7 @@ FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function 
 
 all: $(LIB)
 
-build/%.o: vaeunet_amd/csrc/%.hip vaeunet_amd/csrc/common.h vaeunet_amd/csrc/host.h vaeunet_amd/csrc/attn_pre.h vaeunet_amd/csrc/bn_bwd_elem.h vaeunet_amd/csrc/reflect.h vaeunet_amd/csrc/lds_hist.h include/vaeunet.h
+build/%.o: vaeunet_amd/csrc/%.hip $(wildcard vaeunet_amd/csrc/*.h) include/vaeunet.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 

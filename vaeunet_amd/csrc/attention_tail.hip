@@ -21,11 +21,10 @@
 #include <type_traits>
 
 #include "host.h"
+#include "wave.h"
 #include "attn_pre.h"
 
 namespace {
-
-VU_DEV uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
 
 enum { Q_SG, Q_TG, Q_SX, Q_TX, Q_WP, Q_MG, Q_AG, Q_BG, Q_EG, Q_MX, Q_AX, Q_BX, Q_EX, NQ };
 
@@ -201,8 +200,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_tail_kernel(Att
     auto add_old = [&](u32x4& v, const u32x4 o) {
 #pragma unroll
       for (int w = 0; w < 4; ++w)
-        v[w] = pack2(__uint_as_float(o[w] << 16) + __uint_as_float(v[w] << 16),
-                     __uint_as_float(o[w] & 0xffff0000u) + __uint_as_float(v[w] & 0xffff0000u));
+        v[w] = pack2(lo_f(o[w]) + lo_f(v[w]), hi_f(o[w]) + hi_f(v[w]));
     };
     // one dgrad GEMM and its epilogue: gemm_stream_kernel's MFMA order and
     // GS = 4 store pass.  OLD 0: plain store; 1: the destination's old value
@@ -278,8 +276,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_tail_kernel(Att
                   // gate_bwd_u_kernel's dx = dout * psi, rounded to bf16
 #pragma unroll
                   for (int w = 0; w < 4; ++w)
-                    o[gi][h][w] = pack2(__uint_as_float(o[gi][h][w] << 16) * pv[f],
-                                        __uint_as_float(o[gi][h][w] & 0xffff0000u) * pv[f]);
+                    o[gi][h][w] = pack2(lo_f(o[gi][h][w]) * pv[f], hi_f(o[gi][h][w]) * pv[f]);
                 }
                 add_old(c[gi][h], o[gi][h]);
               }

@@ -30,23 +30,17 @@
 //     acc * x_scale * w_scale[co] (+ bias), bf16 rounding, per-wave (sum,
 //     centered M2) over its 128 pixels, 16-byte NHWC stores.
 #include "host.h"
+#include "wave.h"
 
 #include <cstring>
 
-static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page8[16];
-
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <int BN> struct PP;
-template <> struct PP<256> { static constexpr int WM = 2, WN = 4, TH = 8, TW = 32; };
-template <> struct PP<128> { static constexpr int WM = 4, WN = 2, TH = 16, TW = 32; };
-template <> struct PP<64> { static constexpr int WM = 8, WN = 1, TH = 32, TW = 32; };
-
-VU_DEV void wait_vm(int n) {
+// at most n (0..7) vector-memory operations outstanding (n folds to a constant)
+VU_DEV void wait_vm_n(int n) {
   switch (n) {
     case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
     case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
@@ -59,18 +53,6 @@ VU_DEV void wait_vm(int n) {
   }
 }
 
-VU_DEV void pp_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int R>
-VU_DEV float ror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + R, 0xf, 0xf, false));
-}
 // sum over the 32 lanes of a half-wave (every lane receives the total): DPP
 // row sums, then v_permlane16_swap pairs rows 0/1 and 2/3 (a VALU exchange;
 // a __shfl_xor across rows is an LDS ds_bpermute round trip)
@@ -79,8 +61,6 @@ VU_DEV float half32_sum(float v) {
   const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
-
-VU_DEV uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
 
 // min / max over the 32 lanes of a half-wave (VuConvFp8.stat_min / stat_max):
 // the half32_sum network with fminf / fmaxf
@@ -109,15 +89,6 @@ VU_DEV float half32_min(float v) {
 // array (31 exchanges in all instead of 32 five-step row reductions).  Lane
 // bit 4 by v_permlane16_swap, 3 by row_ror:8, 2 by row_half_mirror +
 // quad reversal, 1 and 0 by quad permutations (all VALU: no LDS crossbar).
-template <int CTRL>
-VU_DEV float dmov(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-VU_DEV float lx1(float v) { return dmov<0xB1>(v); }             // lane ^ 1
-VU_DEV float lx2(float v) { return dmov<0x4E>(v); }             // lane ^ 2
-VU_DEV float lx4(float v) { return dmov<0x1B>(dmov<0x141>(v)); }  // lane ^ 4
-VU_DEV float lx8(float v) { return dmov<0x128>(v); }            // lane ^ 8 (row_ror:8)
-
 VU_DEV float bfly32_reduce(const float (&v)[32], int lane) {
   const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
   float w[16], x[8], y[4], z[2];
@@ -272,7 +243,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
   const int gt = tid & 255;
   const int gw = wid & 3;
   const uint8_t* bmat = reinterpret_cast<const uint8_t*>(p.w);
-  const void* zp = (const void*)vu_zero_page8;
+  const void* zp = (const void*)vu_zero_page;
   char* const hbuf = smem;
   char* const wbuf = smem + 2 * HALO;
 
@@ -315,7 +286,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
         const void* gp = zp;
         if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W)
           gp = h.src + ((int64_t)(h.img * H + y) * W + x) * h.st + pswz(px, P & 3);
-        __builtin_amdgcn_global_load_lds(gp, (lds_void*)(h.hb + (k * 256 + gw * 64) * 16), 16, 0, 0);
+        dma16(gp, h.hb + (k * 256 + gw * 64) * 16);
       }
     }
   };
@@ -338,7 +309,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
       const int P = k * 256 + gt;
       const int row = P >> 2;
       const void* gp = bmat + (int64_t)(n0w_ + row) * p.ldw + kb + pswz(row, P & 3);
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(B + (k * 256 + gw * 64) * 16), 16, 0, 0);
+      dma16(gp, B + (k * 256 + gw * 64) * 16);
     }
   };
 
@@ -442,8 +413,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
     wnext();
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  pp_barrier();
-  if (grp) pp_barrier();  // the stagger: half 1 runs one barrier behind
+  raw_barrier();
+  if (grp) raw_barrier();  // the stagger: half 1 runs one barrier behind
 
   int ti = 0, s = 0;
   for (int gs = 0; gs < S; ++gs) {
@@ -457,7 +428,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) pf[i] = frag32(A, prow[i] + toff, hl);
     if (XM != 2 && !grp && gs + 2 < S) wstage(0, LB0A);
-    pp_barrier();
+    raw_barrier();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -468,7 +439,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
         else
           acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[j], pf[i], acc[i][j], 0, 0, 0, 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
-    pp_barrier();
+    raw_barrier();
 #pragma unroll
     for (int i = 0; i < 2; ++i) pf[i] = frag32(A, prow[2 + i] + toff, hl);
     if (XM == 2) {
@@ -477,7 +448,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
       if (gs + 2 < S) {
         wstage(LB0A, LB0);
         wnext();
-        wait_vm(LB0);
+        wait_vm_n(LB0);
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
@@ -489,7 +460,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
         if (t == 8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
-    pp_barrier();
+    raw_barrier();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -501,14 +472,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_kernel(VuConvFp8 p) {
           acc[2 + i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[j], pf[i], acc[2 + i][j], 0, 0, 0, 0, 0,
                                                                           0);
     __builtin_amdgcn_s_setprio(0);
-    pp_barrier();
+    raw_barrier();
     if (++s == nk) {
       epilogue(ti);
       s = 0;
       ++ti;
     }
   }
-  if (!grp) pp_barrier();
+  if (!grp) raw_barrier();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -572,7 +543,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_pp_kernel(VuConvFp8 p) {
   const int grp = wid >> 2;
   const int gt = tid & 255, gw = wid & 3;
   const uint8_t* bmat = reinterpret_cast<const uint8_t*>(p.w);
-  const void* zp = (const void*)vu_zero_page8;
+  const void* zp = (const void*)vu_zero_page;
   char* const hbuf = smem;
   char* const wbuf = smem + 2 * HALO;
 
@@ -608,7 +579,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_pp_kernel(VuConvFp8 p) {
         const int y = yb - 1 + hy, x = xb - 1 + hx;
         const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
         const void* gp = ok ? (const void*)(src + (int64_t)(y * W + x) * st + pswz(px, P & 3)) : zp;
-        __builtin_amdgcn_global_load_lds(gp, (lds_void*)(hbuf + buf * HALO + (i * 256 + gw * 64) * 16), 16, 0, 0);
+        dma16(gp, hbuf + buf * HALO + (i * 256 + gw * 64) * 16);
       }
     }
   };
@@ -622,7 +593,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_pp_kernel(VuConvFp8 p) {
       const int P = i * 256 + gt;
       const int row = P >> 2;
       const void* gp = (const void*)(wrow0 + (int64_t)row * p.ldw + k0 + pswz(row, P & 3));
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(B + (i * 256 + gw * 64) * 16), 16, 0, 0);
+      dma16(gp, B + (i * 256 + gw * 64) * 16);
     }
   };
 
@@ -653,8 +624,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_pp_kernel(VuConvFp8 p) {
     wstage(cbeg, 1, 1, 0, LB0);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  pp_barrier();
-  if (grp) pp_barrier();
+  raw_barrier();
+  if (grp) raw_barrier();
 
   int hb = 0;
   for (int c = cbeg; c < cend; ++c) {
@@ -678,7 +649,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_pp_kernel(VuConvFp8 p) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) pf[i] = frag32(Ah, prow[i] + toff, hl);
       if (XM != 2 && !grp && pref) wstage(pc, pt, pslot, 0, LB0A);
-      pp_barrier();
+      raw_barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -689,14 +660,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_pp_kernel(VuConvFp8 p) {
           else
             acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[j], pf[i], acc[i][j], 0, 0, 0, 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
-      pp_barrier();
+      raw_barrier();
 #pragma unroll
       for (int i = 0; i < 2; ++i) pf[i] = frag32(Ah, prow[2 + i] + toff, hl);
       if (XM == 2) {
       } else if (!grp) {
         if (pref) {
           wstage(pc, pt, pslot, LB0A, LB0);
-          wait_vm((PD - 1) * LB0);
+          wait_vm_n((PD - 1) * LB0);
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -704,7 +675,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_pp_kernel(VuConvFp8 p) {
         if (t == 0 && next_here) halo_chunk(c + 1, hb ^ 1);
         if (t == 8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      pp_barrier();
+      raw_barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -716,11 +687,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_pp_kernel(VuConvFp8 p) {
             acc[2 + i][j] =
                 __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[j], pf[i], acc[2 + i][j], 0, 0, 0, 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
-      pp_barrier();
+      raw_barrier();
     }
     hb ^= 1;
   }
-  if (!grp) pp_barrier();
+  if (!grp) raw_barrier();
 
   // ---- register epilogue (the persistent kernel's) ---------------------------
   const __attribute__((address_space(4))) VuConvFp8* ep =
@@ -895,7 +866,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_c64_kernel(VuConvFp8 p) {
     s = reinterpret_cast<const uint8_t*>(g.src[q]) + (cb - (q == 0 ? 0 : g.cend[q - 1]));
     stv = g.stride[q];
   };
-  const void* const zp = (const void*)vu_zero_page8;
+  const void* const zp = (const void*)vu_zero_page;
 
   // resident weights: chunk ch, tap block t = 64 rows (output channels) of 64
   // bytes, piece q of row n holding logical piece q ^ ((n>>2)&3) (pswz)
@@ -909,8 +880,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_c64_kernel(VuConvFp8 p) {
         const int s = i * 512 + tid;
         const int tap = s >> 8, row = (s >> 2) & 63;
         const void* gp = (const void*)(bm + (int64_t)row * p.ldw + tap * 64 * NCH + 64 * ch + pswz(row, s & 3));
-        __builtin_amdgcn_global_load_lds(gp, (lds_void*)(wl + ch * C64_WBYTES + (i * 512 + wid * 64) * 16), 16, 0,
-                                         0);
+        dma16(gp, wl + ch * C64_WBYTES + (i * 512 + wid * 64) * 16);
       }
   }
   if (tid < 64) {
@@ -936,7 +906,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_c64_kernel(VuConvFp8 p) {
         const int y = y0 + hy, x = x0 + hx;
         const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
         const void* gp = ok ? (const void*)(s0 + (int64_t)(y * W + x) * st + pswz(px, s & 3)) : zp;
-        __builtin_amdgcn_global_load_lds(gp, (lds_void*)(dst + (i * 512 + wid * 64) * 16), 16, 0, 0);
+        dma16(gp, dst + (i * 512 + wid * 64) * 16);
       }
     }
   };
@@ -992,7 +962,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_c64_kernel(VuConvFp8 p) {
     if (NCH > 1 && ch + 1 < NCH) {
       // more chunks of this tile: only the next step's halo is in flight
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      pp_barrier();
+      raw_barrier();
       b ^= 1;
       continue;
     }
@@ -1118,7 +1088,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_fp8_c64_kernel(VuConvFp8 p) {
       asm volatile("s_waitcnt vmcnt(10)" ::: "memory");  // 2 statistics + 8 output stores
     else
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    pp_barrier();  // (a __syncthreads() would drain the stores too)
+    raw_barrier();  // (a __syncthreads() would drain the stores too)
     b ^= 1;
   }
 }

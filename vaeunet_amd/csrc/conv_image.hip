@@ -17,16 +17,9 @@
 //     pixel: two 16-byte NHWC stores per fragment, BatchNorm partials per
 //     64-pixel wave tile by DPP row sums.
 #include "host.h"
+#include "wave.h"
 
 namespace {
-
-template <int R>
-VU_DEV float ror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + R, 0xf, 0xf, false));
-}
-VU_DEV float row16_sum(float v) { return ror_add<1>(ror_add<2>(ror_add<4>(ror_add<8>(v)))); }
-
-VU_DEV uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
 
 constexpr int NT = 256;  // 4 waves
 constexpr int TP = 64;   // pixels per wave tile (4 fragments; also the BN statistics row tile)
@@ -136,19 +129,10 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_image_kernel(VuGemmFwd p) {
         f32x4 sm, m2;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float sv = 0.f;
-#pragma unroll
-          for (int i = 0; i < NF; ++i) sv += acc[i][j][r];
-          sv = row16_sum(sv);
-          const float mean = sv * (1.f / TP);
-          float v = 0.f;
-#pragma unroll
-          for (int i = 0; i < NF; ++i) {
-            const float d = acc[i][j][r] - mean;
-            v += d * d;
-          }
+          float sv, v;
+          tile_sum_m2(acc, j, r, sv, v);
           sm[r] = sv;
-          m2[r] = row16_sum(v);
+          m2[r] = v;
         }
         if (r16 == 0) {
           *reinterpret_cast<f32x4*>(ss + 4 * j) = sm;

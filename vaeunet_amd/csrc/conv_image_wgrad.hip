@@ -29,11 +29,10 @@
 //
 // BN = false: the same body with dy given (no transform).
 #include "host.h"
+#include "wave.h"
 #include "bn_bwd_elem.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int NT = 256, NW = NT / 64;
 constexpr int TP = 32;            // pixels per wave tile

@@ -19,15 +19,9 @@
 //     BatchNorm partials per 64-pixel wave tile (DPP row sums) and
 //     permlane-regrouped stores of 64 contiguous bytes per pixel.
 #include "host.h"
+#include "wave.h"
 
 namespace {
-
-template <int R>
-VU_DEV float ror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + R, 0xf, 0xf, false));
-}
-VU_DEV float row16_sum(float v) { return ror_add<1>(ror_add<2>(ror_add<4>(ror_add<8>(v)))); }
-VU_DEV uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
 
 constexpr int KR = 7, TAPS = KR * KR;   // 49
 constexpr int KS = (TAPS + 3) / 4;      // 13 K-steps of 4 taps

@@ -22,12 +22,11 @@
 // 16-byte coalesced rows.
 #include <stdlib.h>
 #include "host.h"
+#include "wave.h"
 
 namespace {
 
-constexpr int KB = 128;  // bytes of K per LDS row per k-step
-
-VU_DEV int swz(int row, int chunk) { return row * KB + ((chunk ^ (row & 7)) << 4); }
+constexpr int KB = 128;  // bytes of K per LDS row per k-step (the row of swz())
 
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {

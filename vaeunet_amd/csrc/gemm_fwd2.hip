@@ -21,17 +21,12 @@
 //     coalesced stores; out_mode 1 scatters the ConvTranspose2d(k=2, s=2)
 //     pixel shuffle, out_mode 2 a stride-2 parity lattice.
 #include "host.h"
+#include "wave.h"
 #include <stdlib.h>
-
-static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page[16];  // 16 B of zeros: padding lanes DMA from here
 
 namespace {
 
 constexpr int KB = 128;  // bytes of K per LDS row per step (64 bf16)
-typedef __attribute__((address_space(3))) void lds_void;
-
-VU_DEV int swz(int row, int chunk) { return row * KB + ((chunk ^ (row & 7)) << 4); }
-
 
 template <int BM, int BN, int WM, int WN, int NS, bool SPLIT = false>
 __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_fwd_v2_kernel(VuGemmFwd p) {
@@ -124,12 +119,12 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_fwd_v2_kernel(VuGemmFwd 
       const void* gp = zp;
       if (cin && (unsigned)(rh[i] + dh) < (unsigned)g.Hs && (unsigned)(rw[i] + dw) < (unsigned)g.Ws)
         gp = src + (rpix[i] + dpix) * st;
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(A + (i * NT + wid * 64) * 16), 16, 0, 0);
+      dma16(gp, A + (i * NT + wid * 64) * 16);
     }
 #pragma unroll
     for (int i = 0; i < LB; ++i) {
       const void* gp = (bok[i] && k0 + lchunk_b[i] * EPC < K) ? (const void*)(brow[i] + k0) : zp;
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(B + (i * NT + wid * 64) * 16), 16, 0, 0);
+      dma16(gp, B + (i * NT + wid * 64) * 16);
     }
   };
 

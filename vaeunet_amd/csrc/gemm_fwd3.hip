@@ -23,15 +23,11 @@
 //   * epilogue identical to v1/v2: fp32 tile in LDS, BatchNorm per-tile
 //     (sum, centered M2) on the bf16-rounded values, 16-byte stores.
 #include "host.h"
-
-static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page3[16];
+#include "wave.h"
 
 namespace {
 
 constexpr int KB = 128;  // bytes per LDS row (64 bf16 channels)
-typedef __attribute__((address_space(3))) void lds_void;
-
-VU_DEV int swz(int row, int chunk) { return row * KB + ((chunk ^ (row & 7)) << 4); }
 
 template <int TW>
 struct Geo {
@@ -89,7 +85,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo_kernel(VuGemmFwd p) {
     hpix[i] = ok ? (img * H + y) * W + x : -1;
   }
   const bf16_t* bmat = reinterpret_cast<const bf16_t*>(p.b);
-  const void* zp = (const void*)vu_zero_page3;
+  const void* zp = (const void*)vu_zero_page;
   char* const hbuf = smem;
   char* const bbuf = smem + NHB * HALO;
 
@@ -108,7 +104,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo_kernel(VuGemmFwd p) {
     const int lchunk = pchunk ^ (hp & 7);
     const void* gp = hpix[i] >= 0 ? (const void*)(src + (int64_t)hpix[i] * st + lchunk * 8) : zp;
     char* dst = hbuf + (c % NHB) * HALO + (i * NT + wid * 64) * 16;
-    __builtin_amdgcn_global_load_lds(gp, (lds_void*)dst, 16, 0, 0);
+    dma16(gp, dst);
   };
   auto wstage = [&](int s) {
     const int c = s / 9, t = s - (s / 9) * 9;
@@ -121,7 +117,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_halo_kernel(VuGemmFwd p) {
       int j = n0 + row;
       const void* gp = zp;
       if (j < p.ncol) gp = bmat + (int64_t)j * p.ldb + k0 + lchunk * 8;
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(B + (i * NT + wid * 64) * 16), 16, 0, 0);
+      dma16(gp, B + (i * NT + wid * 64) * 16);
     }
   };
   // DMA instrs issued in loop step u (for the counted waits below)

@@ -42,42 +42,9 @@
 //     writes its fp32 tile to a slab; splitk_finish_kernel sums the slabs in
 //     a fixed order and applies the epilogue above (deterministic).
 #include "host.h"
-
-static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page4[16];
+#include "wave.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int BN> struct PP;
-template <> struct PP<256> { static constexpr int WM = 2, WN = 4, TH = 8, TW = 32; };
-template <> struct PP<128> { static constexpr int WM = 4, WN = 2, TH = 16, TW = 32; };
-template <> struct PP<64> { static constexpr int WM = 8, WN = 1, TH = 32, TW = 32; };
-
-// at most N vector-memory operations of this wave outstanding (loads AND
-// stores: CDNA counts both in vmcnt, in issue order)
-template <int N>
-VU_DEV void wait_vm_c() {
-  static_assert(N >= 0 && N <= 63, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// A workgroup barrier nothing is scheduled across (the ping-pong relies on
-// the exact placement of reads, DMA issues and MFMAs between barriers).
-VU_DEV void pp_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// sum over the 16 lanes of a DPP row (every lane receives the total)
-template <int R>
-VU_DEV float ror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + R, 0xf, 0xf, false));
-}
-VU_DEV float row16_sum(float v) { return ror_add<1>(ror_add<2>(ror_add<4>(ror_add<8>(v)))); }
 
 // RELU: epilogue ReLU (VuGemmFwd.relu).  FULL: one read segment + one
 // 32-MFMA segment per step (2 barriers) instead of two 16-MFMA halves (4
@@ -159,7 +126,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
   const int gt = tid & 255;        // thread index inside the half
   const int gw = wid & 3;          // wave index inside the half
   const bf16_t* bmat = reinterpret_cast<const bf16_t*>(p.b);
-  const void* zp = (const void*)vu_zero_page4;
+  const void* zp = (const void*)vu_zero_page;
   char* const hbuf = smem;
   char* const wbuf = smem + 2 * HALO;
 
@@ -200,7 +167,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
         const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
         const void* gp = ok ? (const void*)(src + (int64_t)(y * W + x) * st) : zp;
         char* dst = hbuf + buf * HALO + (i * 256 + gw * 64) * 16;
-        __builtin_amdgcn_global_load_lds(gp, (lds_void*)dst, 16, 0, 0);
+        dma16(gp, dst);
       }
     }
   };
@@ -214,7 +181,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
       const int P = i * 256 + gt;
       const int row = P >> 2;
       const void* gp = (const void*)(bmat + (int64_t)(dn0 + row) * p.ldb + k0 + (P & 3) * 8);
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(B + (i * 256 + gw * 64) * 16), 16, 0, 0);
+      dma16(gp, B + (i * 256 + gw * 64) * 16);
     }
   };
 
@@ -241,8 +208,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  pp_barrier();
-  if (grp) pp_barrier();  // the stagger: half 1 runs one barrier behind
+  raw_barrier();
+  if (grp) raw_barrier();  // the stagger: half 1 runs one barrier behind
 
   // steps = (chunk c, tap t); a chunk has 9 = 3 x NBW taps, so the weight
   // ring slot of tap t is t % 3 in every chunk
@@ -271,7 +238,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
         if (!grp) {
           if (pref) {
             wstage(pc, pt, pslot, 0, LB0);
-            wait_vm_c<(PD - 1) * LB0>();
+            wait_vm<(PD - 1) * LB0>();
           } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           }
@@ -279,7 +246,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
           if (t == 0 && next_here) halo_chunk(c + 1, hb ^ 1);
           if (t == 8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        pp_barrier();
+        raw_barrier();
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -288,7 +255,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bq[j]),
                                                                 __builtin_bit_cast(bf16x8, aq[i]), acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
-        pp_barrier();
+        raw_barrier();
         continue;
       }
       u32x4 bf[4], af[4];
@@ -299,7 +266,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const u32x4*>(A + arow(i));
       if (!grp && pref) wstage(pc, pt, pslot, 0, LB0A);
-      pp_barrier();
+      raw_barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -308,7 +275,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bf[j]),
                                                               __builtin_bit_cast(bf16x8, af[i]), acc[i][j], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
-      pp_barrier();
+      raw_barrier();
       // -- phase 2: pixel fragments 4..7; half 0 finishes the prefetch and
       //    waits for the next step's weights; half 1 streams the next chunk's
       //    halo and waits for it at the chunk's last tap
@@ -317,7 +284,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
       if (!grp) {
         if (pref) {
           wstage(pc, pt, pslot, LB0A, LB0);
-          wait_vm_c<(PD - 1) * LB0>();  // only the prefetch just issued may be in flight
+          wait_vm<(PD - 1) * LB0>();  // only the prefetch just issued may be in flight
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -325,7 +292,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
         if (t == 0 && next_here) halo_chunk(c + 1, hb ^ 1);
         if (t == 8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      pp_barrier();
+      raw_barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -335,11 +302,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
                                                                   __builtin_bit_cast(bf16x8, af[i]), acc[4 + i][j], 0,
                                                                   0, 0);
       __builtin_amdgcn_s_setprio(0);
-      pp_barrier();
+      raw_barrier();
     }
     hb ^= 1;
   }
-  if (!grp) pp_barrier();  // re-align the halves
+  if (!grp) raw_barrier();  // re-align the halves
 
   // ---- epilogue -------------------------------------------------------------
   // acc[i][j][r]: pixel wm*128 + i*16 + (lane&15), channel n0 + cbase + j*16 + r
@@ -479,7 +446,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(VuGemmFwd p) {
   // issued (measured: the 17 forward layers 2.65 ms with statistics against
   // 2.44 ms without)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  pp_barrier();
+  raw_barrier();
   // fragments 2h and 2h+1 are the 32 pixels of tile row wm*4 + h
   bf16_t* const orow0 = reinterpret_cast<bf16_t*>(ep->out) + ep->out_coff + n0 + wn * 64 +
                         (((int64_t)img * H + y0 + wm * 4) * W + x0) * ep->out_stride;

@@ -23,32 +23,18 @@
 //     start of the tile's last step, before the next stage's DMA, so waiting
 //     for them does not drain the ring.
 #include "host.h"
-
-static __device__ __attribute__((aligned(16))) uint32_t v5_zero_page[16];
+#include "wave.h"
 
 namespace {
 
 constexpr int KB = 128;  // bytes of K per LDS row per step (64 bf16)
 constexpr int BM = 256, WM = 4, WN = 2, NT = WM * WN * 64, NS = 3;
-typedef __attribute__((address_space(3))) void lds_void;
 
-VU_DEV int swz_a(int row, int chunk) { return row * KB + ((chunk ^ (row & 7)) << 4); }
 template <int GS>
 VU_DEV int fb(int row) { return (row & 3) | (((row >> (GS == 4 ? 4 : 3)) & 1) << 2); }
 template <int GS>
 VU_DEV int swz_b(int row, int chunk) { return row * KB + ((chunk ^ fb<GS>(row)) << 4); }
 
-template <int N>
-VU_DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-template <int R>
-VU_DEV float ror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + R, 0xf, 0xf, false));
-}
-VU_DEV float row16_sum(float v) { return ror_add<1>(ror_add<2>(ror_add<4>(ror_add<8>(v)))); }
-VU_DEV uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
-VU_DEV float lo_f(uint32_t w) { return __uint_as_float(w << 16); }
-VU_DEV float hi_f(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
 struct Pix { int n, h, w; bool ok; };
 
@@ -90,7 +76,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p) {
   // the kernel's VALU instructions)
   const FastDiv div_hw((uint32_t)HW), div_w((uint32_t)g.W), div_co((uint32_t)(p.cout > 0 ? p.cout : 1));
   const bf16_t* bmat = reinterpret_cast<const bf16_t*>(p.b);
-  const void* zp = (const void*)v5_zero_page;
+  const void* zp = (const void*)vu_zero_page;
 
   // ---- staging state: the tile / k-step the next stage() call loads ----
   // A lane's rows and chunks are fixed; per (tile, tap, source) SEGMENT of
@@ -144,6 +130,9 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p) {
     }
     char* A = smem + slot * STAGE;
     char* B = A + BM * KB;
+    // (the DMA calls below are dma16() of wave.h spelled out: through the
+    // wrapper the source-pointer cast lands behind the LDS address arithmetic
+    // and the compiler schedules the m0 writes of this kernel differently)
     const int off = seg_step * KST;
     const bool cin = lch_a * 8 < seg_rem - off;  // channel tail of the source
 #pragma unroll
@@ -225,7 +214,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p) {
       const int ch = kk * 4 + gq;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
-        af[kk][i] = *reinterpret_cast<const u32x4*>(A + swz_a(wm * 64 + 16 * i + r16, ch));
+        af[kk][i] = *reinterpret_cast<const u32x4*>(A + swz(wm * 64 + 16 * i + r16, ch));
 #pragma unroll
       for (int j = 0; j < TN; ++j)
         bf[kk][j] = *reinterpret_cast<const u32x4*>(B + swz_b<GS>(wn * WNC + wrow(j, r16), ch));
@@ -273,19 +262,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_fwd_v5_kernel(VuGemmFwd p) {
         f32x4 sm, m2;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float sv = 0.f;
-#pragma unroll
-          for (int i = 0; i < TM; ++i) sv += acc[i][j][r];
-          sv = row16_sum(sv);
-          const float mean = sv * (1.f / 64.f);
-          float v = 0.f;
-#pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            const float d = acc[i][j][r] - mean;
-            v += d * d;
-          }
+          float sv, v;
+          tile_sum_m2(acc, j, r, sv, v);
           sm[r] = sv;
-          m2[r] = row16_sum(v);
+          m2[r] = v;
         }
         if (r16 == 0) {
           *reinterpret_cast<f32x4*>(p.stat_sum + (int64_t)srow * p.ncol + col0 + 4 * j) = sm;

@@ -31,12 +31,9 @@
 //     position (k + 2 * ((P >> 2) & 1)) & 3, which spreads the 16 lanes of
 //     every ds_read_b128 lane group over distinct banks for any tap shift.
 #include "host.h"
-
-static __device__ __attribute__((aligned(16))) uint32_t v6_zero_page[16];
+#include "wave.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int TH = 16, TW = 32;
 constexpr int HWD = TW + 2;                  // halo row (pixels)
@@ -51,21 +48,6 @@ constexpr int LDS_BYTES = WBYTES + 2 * HBUF;
 static_assert(LDS_BYTES <= 163840, "LDS");
 static_assert(WROUNDS * 512 * 16 == WBYTES, "weight DMA rounds");
 
-template <int N>
-VU_DEV void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// a workgroup barrier that neither drains the memory counters nor lets the
-// compiler move LDS reads, DMA issues or MFMAs across it
-VU_DEV void raw_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 // weight-row piece swizzle: with the permuted fragment rows below (lane row
 // rr of fragment j = channel 16*(rr>>2) + 4j + (rr&3)) every ds_read_b128
 // lane group touches 16 distinct 4-bank groups (checked for all j, tap, c)
@@ -75,16 +57,8 @@ VU_DEV int wswz(int n) { return (n + (n >> 2)) & 7; }
 // ---- butterfly transpose-reduce over the 16 lanes of a DPP row ----------
 // v[k] (16 slots per lane) -> lane m of the row holds the sum over the row's
 // lanes of slot m: each step pairs lanes across one lane bit and halves the
-// array (15 lane moves instead of 16 four-step rotate-add reductions, 64)
-template <int CTRL>
-VU_DEV float dmov(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-VU_DEV float lx1(float v) { return dmov<0xB1>(v); }               // lane ^ 1
-VU_DEV float lx2(float v) { return dmov<0x4E>(v); }               // lane ^ 2
-VU_DEV float lx4(float v) { return dmov<0x1B>(dmov<0x141>(v)); }  // lane ^ 4
-VU_DEV float lx8(float v) { return dmov<0x128>(v); }              // lane ^ 8 (row_ror:8)
-
+// array (15 lane moves instead of 16 four-step rotate-add reductions, 64;
+// lx1..lx8 of wave.h)
 VU_DEV float bfly16_reduce(const float (&v)[16], int lane) {
   const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
   float x[8], y[4], z[2];
@@ -154,7 +128,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_kernel(VuGemmFwd p) {
   const int l16 = lane & 15, kg = lane >> 4;
   const bf16_t* const src = reinterpret_cast<const bf16_t*>(g.src[0]);
   const int64_t st = g.stride[0];
-  const void* const zp = (const void*)v6_zero_page;
+  const void* const zp = (const void*)vu_zero_page;
   // bias of this lane's channels, loaded up front: a load in the epilogue
   // would wait for the in-flight halo DMA (vmcnt is in order)
   f32x4 bv[4];
@@ -171,7 +145,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_kernel(VuGemmFwd p) {
       const int s = i * 512 + tid;
       const int n = s / 72, pc = s - (s / 72) * 72;
       const void* gp = (const void*)(bm + (int64_t)n * p.ldb + (pc ^ wswz(n)) * 8);
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(wl + (i * 512 + wid * 64) * 16), 16, 0, 0);
+      dma16(gp, wl + (i * 512 + wid * 64) * 16);
     }
   }
   // ---- halo of (tile t, chunk c) into buffer b ----
@@ -191,7 +165,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_kernel(VuGemmFwd p) {
       const int k = (pos - ((P >> 1) & 2)) & 3;  // the global piece stored at position pos
       const bool ok = s < HPIECES && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
       const void* gp = ok ? (const void*)(s0 + (int64_t)(y * W + x) * st + k * 8) : zp;
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(dst + (i * 512 + wid * 64) * 16), 16, 0, 0);
+      dma16(gp, dst + (i * 512 + wid * 64) * 16);
     }
   };
 
@@ -424,7 +398,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64s_kernel(VuGemmFwd p) {
   const int l16 = lane & 15, kg = lane >> 4;
   const bf16_t* const src = reinterpret_cast<const bf16_t*>(g.src[0]);
   const int64_t st = g.stride[0];
-  const void* const zp = (const void*)v6_zero_page;
+  const void* const zp = (const void*)vu_zero_page;
   const bool has_bias = p.bias != nullptr;
   if (tid < 64) bias_l[tid] = has_bias ? p.bias[tid] : 0.f;  // read from LDS in the epilogue
 
@@ -435,7 +409,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64s_kernel(VuGemmFwd p) {
       const int s = i * 512 + tid;
       const int n = s / 72, pc = s - (s / 72) * 72;
       const void* gp = (const void*)(bm + (int64_t)n * p.ldb + (pc ^ wswz(n)) * 8);
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(wl + (i * 512 + wid * 64) * 16), 16, 0, 0);
+      dma16(gp, wl + (i * 512 + wid * 64) * 16);
     }
   }
   auto halo = [&](int t, int c, int b) {
@@ -454,7 +428,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64s_kernel(VuGemmFwd p) {
       const int k = (pos - ((P >> 1) & 2)) & 3;
       const bool ok = s < HPIECES && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
       const void* gp = ok ? (const void*)(s0 + (int64_t)(y * W + x) * st + k * 8) : zp;
-      __builtin_amdgcn_global_load_lds(gp, (lds_void*)(dst + (i * 512 + wid * 64) * 16), 16, 0, 0);
+      dma16(gp, dst + (i * 512 + wid * 64) * 16);
     }
   };
 

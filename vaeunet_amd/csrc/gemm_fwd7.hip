@@ -38,8 +38,8 @@
 //     split-K slab for splitk_finish_kernel (gemm_fwd4.hip), for the 16^2
 //     level whose 128 tiles are half a chip.
 #include "host.h"
+#include "wave.h"
 
-static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page7[16];
 // XM 5 (timing diagnostic): per wave of blocks < SG_DBG_BLOCKS, cycle totals of
 // the phases [prologue, fragment reads + DMA waits, barrier 1, MFMA issue,
 // barrier 2, epilogue, steps, 0] (tools/enc_bench.py --phases)
@@ -47,22 +47,6 @@ constexpr int SG_DBG_BLOCKS = 64;
 static __device__ unsigned long long vu_sg_dbg[SG_DBG_BLOCKS * 8 * 8];
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int N>
-VU_DEV void wait_vm() {
-  static_assert(N >= 0 && N <= 63, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-VU_DEV void sg_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 // Fragment reads as inline asm: through plain LDS loads the compiler's
 // waitcnt pass, which cannot see the explicit lgkmcnt wait of phase 1, puts an
@@ -80,14 +64,6 @@ VU_DEV u32x4 lds_rd_off(uint32_t a) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(a), "n"(OFF));
   return r;
 }
-VU_DEV void tie(u32x4& v) { asm volatile("" : "+v"(v)); }
-VU_DEV uint32_t lds_addr(const char* p) { return (uint32_t)(uintptr_t)(const lds_void*)p; }
-
-template <int R>
-VU_DEV float ror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + R, 0xf, 0xf, false));
-}
-VU_DEV float row16_sum(float v) { return ror_add<1>(ror_add<2>(ror_add<4>(ror_add<8>(v)))); }
 
 template <int TW, int BN, int NBW>
 struct SG {
@@ -163,7 +139,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_sg_kernel(VuGemmFwd p) {
   const int q = wid & 3;     // pixel quarter (32 pixels) of the tile
   const int gt = tid & 255;
   const bf16_t* bmat = reinterpret_cast<const bf16_t*>(p.b);
-  const void* zp = (const void*)vu_zero_page7;
+  const void* zp = (const void*)vu_zero_page;
   char* const hbuf = smem;                 // [2 buffers][2 groups][HALO]
   char* const wbuf = smem + 4 * HALO;      // [NBW slots][3 taps][2 groups][WTAP]
 
@@ -227,7 +203,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_sg_kernel(VuGemmFwd p) {
         const void* gp = v >= 0 ? (const void*)((g1 ? sb : sa) + (int64_t)(v >> 3) * (g1 ? tb : ta) + (v & 3) * 8)
                                 : zp;
         char* dst = hbuf + buf * 2 * HALO + (i * 256 + (wid & 3) * 64) * 16;
-        __builtin_amdgcn_global_load_lds(gp, (lds_void*)dst, 16, 0, 0);
+        dma16(gp, dst);
       }
     }
   };
@@ -241,7 +217,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_sg_kernel(VuGemmFwd p) {
       const int tx = i >> 1, gg = i & 1;
       const int k0 = (3 * r + tx) * g.C + (cbeg + 2 * k + gg) * 32;
       char* dst = wbuf + sl * SLOT + (tx * 2 + gg) * WTAP + (wid & 3) * 64 * 16;
-      __builtin_amdgcn_global_load_lds((const void*)(wrow + k0), (lds_void*)dst, 16, 0, 0);
+      dma16((const void*)(wrow + k0), dst);
     }
   };
 
@@ -287,8 +263,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_sg_kernel(VuGemmFwd p) {
   // while step 0 runs; step 0's phase 1 waits for step 1 as every step does)
   if (!grp && S >= PD) wait_vm<(PD - 1) * LB>();
   else wait_vm<0>();
-  sg_barrier();
-  if (grp) sg_barrier();  // the stagger: group 1 runs one barrier behind
+  raw_barrier();
+  if (grp) raw_barrier();  // the stagger: group 1 runs one barrier behind
 
   // ---- main loop ------------------------------------------------------------
   // Step s = tap row r (three taps, 24 MFMAs per wave) of chunk pair k.  Two
@@ -323,7 +299,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_sg_kernel(VuGemmFwd p) {
 #pragma unroll
     for (int j = 0; j < 18; ++j) tie(fr[j]);
     tmark(1);
-    sg_barrier();
+    raw_barrier();
     tmark(2);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -337,7 +313,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_sg_kernel(VuGemmFwd p) {
                                                               0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
     tmark(3);
-    sg_barrier();
+    raw_barrier();
     tmark(4);
     if constexpr (TMR) tph[6] += 1;
     slot = slot == NBW - 1 ? 0 : slot + 1;
@@ -351,7 +327,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_sg_kernel(VuGemmFwd p) {
       ++pk;
     }
   }
-  if (!grp) sg_barrier();  // re-align the groups
+  if (!grp) raw_barrier();  // re-align the groups
   __syncthreads();
 
   // ---- sum the two K groups; every wave finalizes one fragment -------------

@@ -20,20 +20,11 @@
 //     the ConvT pixel shuffle keeps them contiguous), BN partials per wave
 //     tile by DPP row sums, optional accumulate (input gradients).
 #include "host.h"
+#include "wave.h"
 
 namespace {
 
 template <bool B> struct BoolTag { static constexpr bool value = B; };
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int R>
-VU_DEV float ror_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + R, 0xf, 0xf, false));
-}
-VU_DEV float row16_sum(float v) { return ror_add<1>(ror_add<2>(ror_add<4>(ror_add<8>(v)))); }
-
-VU_DEV uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
 
 constexpr int NT = 256;  // 4 waves
 
@@ -139,19 +130,10 @@ __global__ __launch_bounds__(NT, 2) void gemm_stream_kernel(VuGemmFwd p) {
         f32x4 sm, m2;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float sv = 0.f;
-#pragma unroll
-          for (int f = 0; f < NF; ++f) sv += acc[f][j][r];
-          sv = row16_sum(sv);
-          const float mean = sv * (1.f / PX);
-          float v = 0.f;
-#pragma unroll
-          for (int f = 0; f < NF; ++f) {
-            const float d = acc[f][j][r] - mean;
-            v += d * d;
-          }
+          float sv, v;
+          tile_sum_m2(acc, j, r, sv, v);
           sm[r] = sv;
-          m2[r] = row16_sum(v);
+          m2[r] = v;
         }
         if (r16 == 0) {
           const int col = (j / GS) * 16 * GS + 4 * GS * gq + 4 * (j % GS);
@@ -182,8 +164,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_stream_kernel(VuGemmFwd p) {
     auto add_old = [&](u32x4& v, const u32x4 o) {
 #pragma unroll
       for (int w = 0; w < 4; ++w)
-        v[w] = pack2(__uint_as_float(o[w] << 16) + __uint_as_float(v[w] << 16),
-                     __uint_as_float(o[w] & 0xffff0000u) + __uint_as_float(v[w] & 0xffff0000u));
+        v[w] = pack2(lo_f(o[w]) + lo_f(v[w]), hi_f(o[w]) + hi_f(v[w]));
     };
     // Two instantiations of the store pass behind ONE uniform branch: with
     // `if (accumulate) load` inside the loop, the vmcnt(0) the compiler puts
@@ -247,10 +228,10 @@ __global__ __launch_bounds__(NT, 2) void gemm_stream_kernel(VuGemmFwd p) {
 #pragma unroll
             for (int h2 = 0; h2 < GS / 2; ++h2) {
               const f32x4 a = acc[f][2 * h2], b = acc[f][2 * h2 + 1];
-              v[h2] = u32x4{pack2(__uint_as_float(o[h2][0] << 16) + a[0], __uint_as_float(o[h2][0] & 0xffff0000u) + a[1]),
-                            pack2(__uint_as_float(o[h2][1] << 16) + a[2], __uint_as_float(o[h2][1] & 0xffff0000u) + a[3]),
-                            pack2(__uint_as_float(o[h2][2] << 16) + b[0], __uint_as_float(o[h2][2] & 0xffff0000u) + b[1]),
-                            pack2(__uint_as_float(o[h2][3] << 16) + b[2], __uint_as_float(o[h2][3] & 0xffff0000u) + b[3])};
+              v[h2] = u32x4{pack2(lo_f(o[h2][0]) + a[0], hi_f(o[h2][0]) + a[1]),
+                            pack2(lo_f(o[h2][1]) + a[2], hi_f(o[h2][1]) + a[3]),
+                            pack2(lo_f(o[h2][2]) + b[0], hi_f(o[h2][2]) + b[1]),
+                            pack2(lo_f(o[h2][3]) + b[2], hi_f(o[h2][3]) + b[3])};
             }
           }
 #pragma unroll

@@ -16,6 +16,7 @@
 // Split-K over m writes fp32 slabs, reduced in a fixed order (deterministic).
 #include <stdlib.h>
 #include "host.h"
+#include "wave.h"
 
 namespace {
 
@@ -55,8 +56,13 @@ VU_DEV u32x4 gather_t(const VuGather& g, const ColDec& d, int n, int h, int w, b
 }
 
 // ---- LDS image addressing ----
-// bf16: rows of RB bytes (= 2*BI), 32-byte blocks XOR-swizzled by f(m).
-template <int RB> VU_DEV int tr_off(int m, int col) {
+// bf16: rows of RB bytes (= 2*BI: 128 or 256), 32-byte blocks XOR-swizzled by
+// f(m).  At these two row sizes this is tr_off<RB> of wave.h, value for value;
+// it keeps its own spelling (block and f formed before the row product)
+// because the compiler schedules the kernel differently from the shared one,
+// and this kernel is kept on the code it was measured with.
+template <int RB> VU_DEV int tr_off_v1(int m, int col) {
+  static_assert(RB == 128 || RB == 256, "row sizes at which this equals tr_off<RB>");
   int blk = col >> 4;
   int f;
   if (RB == 256) f = (m & 3) | ((m >> 1) & 4);
@@ -69,7 +75,7 @@ template <int BI> struct Img<bf16_t, BI> {
   static constexpr int RB = BI * 2;
   static constexpr int BYTES = BMR * RB;
   // byte offset of the 16-byte chunk holding columns [col, col+8) of row m
-  static VU_DEV int chunk_off(int m, int col) { return tr_off<RB>(m, col); }
+  static VU_DEV int chunk_off(int m, int col) { return tr_off_v1<RB>(m, col); }
 };
 template <int BI> struct Img<float, BI> {
   static constexpr int RB = BI * 4 + 64;  // pad: rows m, m+1 16 banks apart
@@ -188,7 +194,6 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_kernel(VuGemmWgrad p) {
     const char* Pb = smem + cur * BUF;
     const char* Qb = Pb + IP::BYTES;
     if constexpr (sizeof(T) == 2) {
-      typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
       const int q = li >> 2, pp = li & 3;
 #pragma unroll
       for (int ks = 0; ks < BMR / 32; ++ks) {
@@ -198,9 +203,9 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_kernel(VuGemmWgrad p) {
           int col = wi * (BI / 2) + a * 16 + 4 * pp;
           int m = ks * 32 + 8 * g4 + q;
           s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (lds_s16x4*)(Pb + tr_off<IP::RB>(m, col) - 0));
+              (lds_s16x4*)(Pb + tr_off_v1<IP::RB>(m, col) - 0));
           s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (lds_s16x4*)(Pb + tr_off<IP::RB>(m + 4, col)));
+              (lds_s16x4*)(Pb + tr_off_v1<IP::RB>(m + 4, col)));
           u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
           af[a] = u32x4{l2[0], l2[1], h2[0], h2[1]};
         }
@@ -208,8 +213,8 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_kernel(VuGemmWgrad p) {
         for (int b = 0; b < TJ; ++b) {
           int col = wj * (BJ / 2) + b * 16 + 4 * pp;
           int m = ks * 32 + 8 * g4 + q;
-          s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(Qb + tr_off<IQ::RB>(m, col)));
-          s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(Qb + tr_off<IQ::RB>(m + 4, col)));
+          s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(Qb + tr_off_v1<IQ::RB>(m, col)));
+          s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(Qb + tr_off_v1<IQ::RB>(m + 4, col)));
           u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
           bf[b] = u32x4{l2[0], l2[1], h2[0], h2[1]};
         }

@@ -12,27 +12,9 @@
 //     SOURCE column of each lane (the LDS image stays lane-linear);
 //   * deterministic split-K over pixels into fp32 slabs (vu_slab_reduce).
 #include "host.h"
-
-static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page[16];  // per code object
+#include "wave.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// 32-byte block swizzle: a 32-lane half of a transposed read touches 8 rows
-// (4 consecutive + 4 rows 8 apart), one 32-byte block each; f(m) spreads them
-// over the 8 bank blocks of the 256-byte bank window.  Rows >= 256 B: all
-// three row bits; 128-B rows (4 blocks): pairs by parity; 64-B rows (2
-// blocks): the two row quads.
-template <int RB> VU_DEV int fsw(int m) {
-  return RB >= 256 ? ((m & 3) | ((m >> 1) & 4))
-                   : RB == 128 ? (((m >> 1) & 1) | ((m >> 2) & 2)) : ((m >> 3) & 1);
-}
-
-template <int RB> VU_DEV int tr_off(int m, int col) {
-  return m * RB + (((col >> 4) ^ fsw<RB>(m)) << 5) + ((col & 15) << 1);
-}
 
 // Transposed 16-bit LDS read as inline asm.  Through the builtin, the
 // compiler cannot tell these reads from the LDS-DMA destinations still in
@@ -45,13 +27,6 @@ VU_DEV u32x2 tr_read(const char* p) {
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(a) : "memory");
   return r;
 }
-
-// wait until at most N LDS reads are outstanding; the fragments passed are
-// tied to the wait so their consumers cannot be scheduled above it
-template <int N> VU_DEV void lgkm_wait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N > 15 ? 15 : N) : "memory");
-}
-VU_DEV void tie(u32x4& v) { asm volatile("" : "+v"(v)); }
 
 // A DMA slot's fixed column: tap, source and channel, with the source's base
 // pointer (channel offset applied) and pixel stride resolved ONCE into
@@ -208,6 +183,9 @@ __global__ __launch_bounds__(WI * WJ * 64, 1) void gemm_wgrad_v2_kernel(VuGemmWg
   auto stage = [&](int64_t mb, int buf) {
     char* Pb = smem + buf * STAGE;
     char* Qb = Pb + BMR * RBP;
+    // (the DMA calls below are dma16() of wave.h spelled out: through the
+    // wrapper the source-pointer cast lands behind the LDS address arithmetic
+    // and the compiler schedules the m0 writes of this kernel differently)
     if (lin) {
       wcnt += BMR;
       const bool wrapped = wcnt >= gp.W;  // block-uniform

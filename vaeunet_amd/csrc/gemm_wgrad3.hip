@@ -22,13 +22,9 @@
 //     across the split, then one slab write (vu_slab_reduce sums the splits in
 //     a fixed order: deterministic).
 #include "host.h"
-
-static __device__ __attribute__((aligned(16))) uint32_t vu_zero_page_w3[16];
+#include "wave.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 // pixel tile: 128 pixels = 4 x 32, or 8 x 16 for 16-pixel-wide images (the
 // ResNet34 encoder's 16^2 level); the halo row pitch (TW + 2 used) is a
@@ -38,23 +34,12 @@ template <int TW> struct WT {
   static constexpr int TH = TP / TW, HWP = TW == 32 ? 48 : 32, HROWS = TH + 2;
 };
 
-template <int RB> VU_DEV int fsw(int m) {
-  return RB >= 256 ? ((m & 3) | ((m >> 1) & 4)) : (((m >> 1) & 1) | ((m >> 2) & 2));
-}
-template <int RB> VU_DEV int tr_off(int m, int col) {
-  return m * RB + (((col >> 4) ^ fsw<RB>(m)) << 5) + ((col & 15) << 1);
-}
-// logical column of the 16-byte physical chunk pc of row m (source-side swizzle)
-template <int RB> VU_DEV int swz_col(int m, int pc) {
-  return ((((pc >> 1) ^ fsw<RB>(m)) << 1) | (pc & 1)) * 8;
-}
-
 // Transposed LDS reads as inline asm: through the builtin the compiler cannot
 // tell them from the next tile's LDS-DMA destinations and inserts an
 // s_waitcnt vmcnt(0) before the first read of a tile -- right after that
 // tile's successor was issued -- which serialises DMA and MFMA (the double
 // buffer never overlapped).  Ordering is explicit instead: vmcnt + barrier
-// for DMA -> reads, lgkm_wait() + tie() for reads -> MFMAs.
+// for DMA -> reads, lgkm_wait_n() + tie() for reads -> MFMAs.
 //
 // tr_read_o: one such read from a per-lane LDS byte address held in a VGPR
 // plus a compile-time byte offset in the instruction's 16-bit offset field,
@@ -73,10 +58,9 @@ VU_DEV u32x4 tr_frag_o2(uint32_t a, const int off_lo, const int off_hi) {
   u32x2 l2 = tr_read_o(a, off_lo), h2 = tr_read_o(a, off_hi);
   return u32x4{l2[0], l2[1], h2[0], h2[1]};
 }
-VU_DEV uint32_t lds_addr(const char* p) { return (uint32_t)(uintptr_t)(const lds_void*)p; }
 
 // at most n LDS operations outstanding (n folds to a constant after unrolling)
-VU_DEV void lgkm_wait(int n) {
+VU_DEV void lgkm_wait_n(int n) {
   switch (n) {
     case 0: asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); break;
     case 1: asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory"); break;
@@ -96,7 +80,6 @@ VU_DEV void lgkm_wait(int n) {
     default: asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory"); break;
   }
 }
-VU_DEV void tie(u32x4& v) { asm volatile("" : "+v"(v)); }
 
 // Per tile, the fragment-read base addresses of the tile's LDS stage are
 // formed once (14 VGPRs) and every (k-step, tap) read uses the instruction
@@ -138,7 +121,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_halo_kernel(VuGemmWgrad p) {
   const int t_end = t_beg + tps < T ? t_beg + tps : T;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const void* zp = (const void*)vu_zero_page_w3;
+  const void* zp = (const void*)vu_zero_page;
 
   // source of this block's 64-channel x chunk
   const int cb = jc * 64;
@@ -200,6 +183,9 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_halo_kernel(VuGemmWgrad p) {
     }
     char* Pb = smem + buf * STAGE;
     char* Qb = Pb + PB;
+    // (the DMA calls below are dma16() of wave.h spelled out: through the
+    // wrapper the source-pointer cast lands behind the LDS address arithmetic
+    // and the compiler schedules the m0 writes of this kernel differently)
     const int64_t pix0 = ((int64_t)img * H + y0) * W + x0;
     const bf16_t* dtile = dsrc + pix0 * dst_;
 #pragma unroll
@@ -317,7 +303,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_halo_kernel(VuGemmWgrad p) {
       }
       // group g's fragments (and every older read) are complete once only the
       // reads of groups g+1 and g+2 may still be outstanding
-      lgkm_wait(nreads(g + 1) + nreads(g + 2));
+      lgkm_wait_n(nreads(g + 1) + nreads(g + 2));
 #pragma unroll
       for (int a = 0; a < TI; ++a) tie(aq[ks & 1][a]);
 #pragma unroll

@@ -1,7 +1,8 @@
 // Host-side declarations shared by the .hip files: the tuning accessor, the
 // small launch helpers, and every host function one file calls in another.
-// (Device state such as the per-file zero_page arrays cannot be shared: each
-// .hip is its own code object.)
+// (Device state is per code object, each .hip being its own: the LDS-DMA zero
+// page is declared once, in wave.h, as a static array, so every file that
+// uses it gets its own storage.)
 #pragma once
 #include "common.h"
 #include "../../include/vaeunet.h"
