@@ -274,6 +274,18 @@ __global__ void gate_bwd_kernel(const T* dout, int64_t dos, const T* x, int64_t 
   }
 }
 
+// One step of the gate backward's per-lane dot product sum_c dout * x.  ONE
+// text with contraction OFF for both instantiations of gate_bwd_u_kernel: left
+// to the compiler, DX = true became a chain of fused multiply-adds and
+// DX = false packed multiplies and separate adds, so dqpre differed in its
+// last bits with whether dx was asked for (tests/test_gpu_attention_ref.py).
+// Unfused is what DX = false, the instantiation in front of the fused backward
+// tail, already computed.
+VU_DEV float gate_dot_step(float acc, float d, float x) {
+#pragma clang fp contract(off)
+  return acc + d * x;
+}
+
 // gate backward for C <= 512 (one 8-channel chunk per lane), U pixel rows of
 // loads in flight per lane.  DX = false: dx is not written (the fused
 // backward tail re-forms dout * p itself, attention_tail.hip)
@@ -306,7 +318,7 @@ __global__ __launch_bounds__(256) void gate_bwd_u_kernel(const T* dout, int64_t 
       Vec8<T> vo;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        acc += vd[u].get(k) * vx[u].get(k);
+        acc = gate_dot_step(acc, vd[u].get(k), vx[u].get(k));
         if constexpr (DX) vo.set(k, vd[u].get(k) * pv[u]);
       }
       if constexpr (DX)
