@@ -19,6 +19,20 @@
  *   stats   : BatchNorm partial statistics are (sum, centered M2) per
  *             (row-tile, channel); they are combined in fp64 with Chan's
  *             formula, in a fixed order (bitwise reproducible).
+ *
+ * This file is also the source of the Python binding: vaeunet_amd/_lib.py
+ * parses it at import (comments and preprocessor lines stripped) and refuses,
+ * with a ValueError, any declaration outside these forms:
+ *   typedef struct [Tag] { <fields> } Name;   fields `T a;`, `T a, b, c;`,
+ *       `T a[3];`, `const T* p;` (one declarator per pointer field), `Name n;`
+ *       of an earlier struct by value; no bit-fields, unions or nested bodies
+ *   <ret> vu_NAME(<args>);   ret one of void / the scalars below; args `T x`,
+ *       `const T* p`, `T* p`, `Name s`, `const Name* s`, or `void` for none
+ *   #define VU_NAME <integer literal>   (no other VU_* macro; beside it only
+ *       the include guard, #include and the extern "C" wrapper below: no #if)
+ *   T: int, int32_t, int64_t, uint32_t, uint64_t, float, double; pointers
+ *       also to void and uint8_t.  No function pointers, no `struct X`
+ *       without a typedef, no pointer to pointer, no other type names.
  */
 #ifndef VAEUNET_H
 #define VAEUNET_H
@@ -353,7 +367,7 @@ int vu_permute4(const float* in, int64_t base, int64_t s0, int64_t s1,
  * ceil(numel / vu_permute4_chunk()) blocks).  chunk0 = prefix block count,
  * nchunks = total blocks. */
 typedef struct VuPermJob {
-  const float* in;
+  const float* inp;
   int64_t base, s0, s1, s2, s3;
   int32_t d0, d1, d2, d3, d3v, dtype;
   void* out;

@@ -13,9 +13,10 @@ import math
 import torch
 
 from ref_small import C_SUM, TILE, U32, bnb_partials_ref
+from vaeunet_amd import _lib
 
 F32, BF16 = torch.float32, torch.bfloat16
-KEY_ATTN = 22            # VU_TUNE_ATTN: 1 batched kernels (default), 0 one-row kernels
+KEY_ATTN = _lib.VU_TUNE_ATTN   # 1 batched kernels (default), 0 one-row kernels
 MAXB = 1024              # grid cap of the psi backward (vu_attn_psi_bwd_blocks)
 EDGE = 1e-3              # bn_near_zero's cancellation criterion
 

@@ -14,10 +14,11 @@ import torch
 
 from ref_small import (C_SUM, U32, bn_bwd_finish_ref, bn_coef_inputs, bn_near_zero, bnb_partials_ref,
                        condition_bn_input)
+from vaeunet_amd import _lib
 
 F32, BF16 = torch.float32, torch.bfloat16
 U_STORE = {F32: 2.0 ** -24, BF16: 2.0 ** -8}
-KEY_BN_NT_MB, KEY_BN_MINBLK = 15, 25     # VU_TUNE_* (include/vaeunet.h)
+KEY_BN_NT_MB, KEY_BN_MINBLK = _lib.VU_TUNE_BN_NT_MB, _lib.VU_TUNE_BN_MINBLK
 UNR = 4                                  # rows in flight per thread (bn.hip)
 MOM, EPS = 0.1, 1e-5
 

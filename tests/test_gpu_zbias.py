@@ -10,10 +10,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from vaeunet_amd import _lib
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 CL = torch.channels_last
-TUNE_V4_MIN_BLOCKS, TUNE_V4_SPLITK, TUNE_GEN = 0, 6, 12
+TUNE_V4_MIN_BLOCKS, TUNE_V4_SPLITK, TUNE_GEN = _lib.VU_TUNE_V4_MIN_BLOCKS, _lib.VU_TUNE_V4_SPLITK, _lib.VU_TUNE_GEN
 TUNE_DEFAULTS = ((TUNE_V4_MIN_BLOCKS, 256), (TUNE_V4_SPLITK, 1), (TUNE_GEN, 4))
 
 

@@ -24,12 +24,17 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from vaeunet_amd._lib import BF16, F32, VuConvFp8, VuGemmFwd, VuGemmWgrad, lib  # noqa: E402
+# tuning keys: the header's numbers (the binding reads them from include/vaeunet.h)
+from vaeunet_amd._lib import (  # noqa: E402
+    VU_TUNE_ATTN as ATTN, VU_TUNE_BN_MINBLK as BN_MINBLK, VU_TUNE_BN_NT_MB as BN_NT_MB, VU_TUNE_FP8_C64 as FP8_C64,
+    VU_TUNE_FP8_GRID as FP8_GRID, VU_TUNE_FP8_PP as FP8_PP, VU_TUNE_FP8_SPLIT as FP8_SPLIT, VU_TUNE_FP8_XM as FP8_XM,
+    VU_TUNE_GEN as GEN, VU_TUNE_PP_FULL as PP_FULL, VU_TUNE_SLAB4 as SLAB4, VU_TUNE_STREAM as STREAM,
+    VU_TUNE_UNSAFE as UNSAFE, VU_TUNE_V2_SMALL as V2_SMALL, VU_TUNE_V4_MIN_BLOCKS as V4_MIN_BLOCKS,
+    VU_TUNE_V4_SPLIT_CHUNKS as V4_SPLIT_CHUNKS, VU_TUNE_V4_SPLITK as V4_SPLITK, VU_TUNE_V5 as V5, VU_TUNE_V6 as V6,
+    VU_TUNE_V6_STAG as V6_STAG, VU_TUNE_V6_XM as V6_XM, VU_TUNE_V7 as V7, VU_TUNE_V7_NBW as V7_NBW,
+    VU_TUNE_V7_XM as V7_XM, VU_TUNE_W2_BIG as W2_BIG, VU_TUNE_W3_SMALL as W3_SMALL)
 
-# tuning keys (include/vaeunet.h) and their defaults
-V4_MIN_BLOCKS, FP8_GRID, STREAM, V4_SPLITK, V4_SPLIT_CHUNKS, V2_SMALL, V5, V6 = 0, 4, 5, 6, 8, 9, 10, 11
-GEN, SLAB4, BN_NT_MB, V7, V7_NBW, V7_XM, W3_SMALL, FP8_XM, FP8_PP, ATTN = 12, 13, 15, 16, 17, 18, 19, 20, 21, 22
-FP8_C64, FP8_SPLIT, BN_MINBLK, PP_FULL, W2_BIG, V6_XM = 23, 24, 25, 27, 28, 29
-UNSAFE, V6_STAG = 33, 34
+# the defaults (the header has none: csrc/tuning.hip holds them)
 DEFAULTS = {V4_MIN_BLOCKS: 256, FP8_GRID: 0, STREAM: 1, V4_SPLITK: 1, V4_SPLIT_CHUNKS: 2, V2_SMALL: 1, V5: 1, V6: 1,
             GEN: 4, SLAB4: 1, BN_NT_MB: 32, V7: 1, V7_NBW: 3, V7_XM: 0, W3_SMALL: 1, FP8_XM: 0, FP8_PP: 1, ATTN: 1,
             FP8_C64: 2, FP8_SPLIT: 1, BN_MINBLK: 256, PP_FULL: 1, W2_BIG: 0, V6_XM: 0,

@@ -1,11 +1,16 @@
-"""ctypes binding of the C-ABI library ``libvaeunet_hip.so`` (include/vaeunet.h).
+"""ctypes binding of the C-ABI library ``libvaeunet_hip.so``, derived from
+its header ``include/vaeunet.h`` when this module is imported: the structs,
+the prototypes and the integer ``VU_*`` constants are declared there and
+nowhere else.
 
 This is the only place the product path touches native code.  There is no
-CPU or PyTorch fallback: if the library is missing or a launch fails the call
-raises, loudly (the oracle under ``oracle/`` is test infrastructure only).
+CPU or PyTorch fallback: if the library or the header is missing or a launch
+fails the call raises, loudly (the oracle under ``oracle/`` is test
+infrastructure only).
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -15,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libvaeunet_hip.so")
 # alternative library file; the product never sets it
 if os.environ.get("VU_LIB_PATH"):
     LIB_PATH = os.environ["VU_LIB_PATH"]
+HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "vaeunet.h")
 
 F32, BF16 = 0, 1
 
@@ -23,218 +29,122 @@ _i = C.c_int
 _l = C.c_int64
 _f = C.c_float
 
+# The one type map.  A pointer to anything but a parsed struct is c_void_p.
+_SCALARS = {"int": _i, "int32_t": C.c_int32, "int64_t": _l, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "float": _f, "double": C.c_double}
+_POINTEES = set(_SCALARS) | {"void", "uint8_t"}
+# Structs whose tables live in device memory: callers hold an address, not a
+# ctypes object, so a pointer to one of these stays c_void_p as well.
+_DEVICE_TABLES = {"VuPermJob", "VuMtEntry"}
 
-class VuGather(C.Structure):
-    _fields_ = [("src", _p * 3), ("stride", _l * 3), ("cend", C.c_int32 * 3),
-                ("nsrc", C.c_int32), ("C", C.c_int32),
-                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
-                ("Hs", C.c_int32), ("Ws", C.c_int32), ("R", C.c_int32), ("S", C.c_int32),
-                ("sy", C.c_int32), ("sx", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
-                ("oy", C.c_int32), ("ox", C.c_int32)]
-
-
-class VuGemmFwd(C.Structure):
-    _fields_ = [("a", VuGather), ("b", _p), ("ldb", _l), ("ncol", C.c_int32),
-                ("out_mode", C.c_int32), ("out", _p), ("out_stride", _l),
-                ("out_coff", C.c_int32), ("oH", C.c_int32), ("oW", C.c_int32),
-                ("opy", C.c_int32), ("opx", C.c_int32), ("cout", C.c_int32),
-                ("bias", _p), ("stat_sum", _p), ("stat_m2", _p), ("accumulate", C.c_int32),
-                ("ksplit", C.c_int32), ("workspace", _p),
-                ("bnb_x", _p), ("bnb_xstride", _l), ("bnb_scale", _p), ("bnb_shift", _p),
-                ("bnb_mean", _p), ("bnb_invstd", _p), ("bnb_part", _p), ("bnb_relu", C.c_int32),
-                ("relu", C.c_int32), ("zbias", _p)]
+_STRUCT = re.compile(r"\s*typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_PROTO = re.compile(r"\s*([\w\s]+?)\s*\b(vu_\w+)\s*\(([^;{}()]*)\)\s*;")
+_NAME = r"\w+(?:\s*\[\s*\d+\s*\])?"
+_FIELD = re.compile(r"\s*(?:const\s+)?(\w+)(\s*\*\s*|\s+)(%s(?:\s*,\s*%s)*)\s*$" % (_NAME, _NAME))
+_ARG = re.compile(r"\s*(?:const\s+)?(\w+)(?:(\s*\*\s*|\s+)(\w+)?)?\s*$")
+_DEFINE = re.compile(r"\s*#\s*define\s+(VU_\w*)(.*)$")
+# the include guard, #include and the extern "C" wrapper; no other conditional
+_DIRECTIVE = re.compile(r"\s*#\s*(?:include|define|ifndef|endif|ifdef\s+__cplusplus)\b")
 
 
-class VuGemmWgrad(C.Structure):
-    _fields_ = [("p", VuGather), ("q", VuGather), ("ni", C.c_int32), ("nj", C.c_int32),
-                ("splits", C.c_int32), ("m_per_split", _l), ("out", _p)]
+def _refuse(decl):
+    return ValueError(f"include/vaeunet.h: declaration outside the forms the binding reads: {' '.join(decl.split())!r}")
 
 
-class VuConvFp8(C.Structure):
-    _fields_ = [("a", VuGather), ("w", _p), ("ldw", _l), ("ncol", C.c_int32), ("out_coff", C.c_int32),
-                ("x_scale", _p), ("w_scale", _p), ("bias", _p), ("out", _p), ("out_stride", _l),
-                ("stat_sum", _p), ("stat_m2", _p), ("workspace", _p), ("stat_min", _p), ("stat_max", _p)]
+def _ctype(base, pointer, structs, decl):
+    if pointer:
+        if base in structs:
+            return _p if base in _DEVICE_TABLES else C.POINTER(structs[base])
+        if base in _POINTEES:
+            return _p
+    elif base in structs:
+        return structs[base]
+    elif base in _SCALARS:
+        return _SCALARS[base]
+    raise _refuse(decl)
 
 
-class VuPermJob(C.Structure):
-    _fields_ = [("inp", _p), ("base", _l), ("s0", _l), ("s1", _l), ("s2", _l), ("s3", _l),
-                ("d0", C.c_int32), ("d1", C.c_int32), ("d2", C.c_int32), ("d3", C.c_int32),
-                ("d3v", C.c_int32), ("dtype", C.c_int32), ("out", _p), ("chunk0", _l),
-                ("q", C.c_int32), ("pad_", C.c_int32)]
+def _struct(name, body, structs):
+    fields = []
+    for decl in body.split(";"):
+        if not decl.strip():
+            continue
+        m = _FIELD.match(decl)
+        # `float* a, b` declares b a float in C: too easy to misread, refused
+        if not m or ("*" in m.group(2) and "," in m.group(3)):
+            raise _refuse(decl)
+        ct = _ctype(m.group(1), "*" in m.group(2), structs, decl)
+        for d in m.group(3).split(","):
+            fname, _, n = d.replace("]", "").partition("[")
+            fields.append((fname.strip(), ct * int(n) if n else ct))
+    return type(name, (C.Structure,), {"_fields_": fields})
 
 
-class VuMtEntry(C.Structure):
-    _fields_ = [("param", _p), ("grad", _p), ("exp_avg", _p), ("exp_avg_sq", _p),
-                ("numel", _l), ("chunk0", _l), ("step_size", _f), ("bc2_sqrt", _f)]
+def _proto(ret, args, structs, decl):
+    if ret != "void" and ret not in _SCALARS:
+        raise _refuse(decl)
+    argtypes = []
+    for a in ([] if args.strip() in ("", "void") else args.split(",")):
+        m = _ARG.match(a)
+        if not m:
+            raise _refuse(decl)
+        argtypes.append(_ctype(m.group(1), "*" in (m.group(2) or ""), structs, decl))
+    return (None if ret == "void" else _SCALARS[ret]), argtypes
 
 
-class VuLatentJob(C.Structure):
-    _fields_ = [("w", _p), ("bias", _p), ("gamma", _p), ("beta", _p), ("running_mean", _p),
-                ("running_var", _p), ("num_batches_tracked", _p), ("momentum", _f), ("eps", _f),
-                ("train", C.c_int32), ("co", C.c_int32), ("cpad", C.c_int32), ("HW", C.c_int32),
-                ("out", _p), ("out_stride", _l), ("y", _p), ("coef", _p), ("block0", _l),
-                ("cgroups", C.c_int32), ("grad_acc", C.c_int32), ("dmap", _p), ("dmap_stride", _l),
-                ("part", _p), ("sblock0", _l), ("dw", _p), ("dbias", _p), ("dgamma", _p), ("dbeta", _p),
-                ("act", _p)]
+def parse_header(text):
+    """C header text -> (structs, prototypes, constants), each a dict by name:
+    ``typedef struct [Tag] { ... } Name;`` as a ctypes.Structure subclass,
+    ``<ret> vu_name(<args>);`` as (restype, argtypes), ``#define VU_NAME
+    <integer>`` as an int.  Anything else raises ValueError quoting the
+    declaration: nothing is guessed and nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts, lines = {}, []
+    for line in text.split("\n"):
+        if not line.lstrip().startswith("#"):
+            lines.append(line)
+            continue
+        m = _DEFINE.match(line)
+        if line.rstrip().endswith("\\") or not _DIRECTIVE.match(line):
+            raise _refuse(line)
+        if m:
+            try:
+                consts[m.group(1)] = int(m.group(2).strip(), 0)
+            except ValueError:
+                raise _refuse(line) from None
+    text, wrapped = re.subn(r'extern\s+"C"\s*\{', "", "\n".join(lines), count=1)
+    text = text.rstrip()
+    if wrapped and text.endswith("}"):
+        text = text[:-1]
+    structs, sigs, pos = {}, {}, 0
+    while True:
+        m = _STRUCT.match(text, pos)
+        if m:
+            structs[m.group(2)] = _struct(m.group(2), m.group(1), structs)
+        else:
+            m = _PROTO.match(text, pos)
+            if not m:
+                break
+            sigs[m.group(2)] = _proto(m.group(1), m.group(3), structs, m.group(0))
+        pos = m.end()
+    if text[pos:].strip():   # whatever neither form matches whole
+        raise _refuse(text[pos:].split(";")[0][:200])
+    return structs, sigs, consts
 
 
-class VuZbJob(C.Structure):
-    _fields_ = [("w", _p), ("ws_co", _l), ("ws_ci", _l), ("ws_ky", _l), ("ws_kx", _l), ("cz0", C.c_int32),
-                ("L", C.c_int32), ("co", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("act", _p),
-                ("row_scale", _p), ("table", _p), ("dy", _p), ("dy_stride", _l), ("rs", _p), ("part", _p),
-                ("dw", _p), ("grad_acc", C.c_int32), ("rs_ready", C.c_int32), ("block0", _l)]
+def _load_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"vaeunet_amd: C header {os.path.normpath(HEADER_PATH)} is missing; the binding is derived "
+                           "from it and the package runs in-tree (no fallback)")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
 
 
-class VuLatentHeads(C.Structure):
-    _fields_ = [("z", _p), ("eps", _p), ("logvar", _p), ("dmu_in", _p), ("dlv_in", _p), ("dz_in", _p), ("pooled", _p),
-                ("w_mu", _p), ("w_lv", _p), ("dw_mu", _p), ("db_mu", _p), ("dw_lv", _p), ("db_lv", _p),
-                ("dpooled", _p), ("C", C.c_int32), ("grad_acc", C.c_int32)]
-
-
-# name -> (restype, argtypes)
-_SIGS = {
-    "vu_gemm_fwd": (_i, [C.POINTER(VuGemmFwd), _i, _p]),
-    "vu_gemm_fwd_row_tile": (_l, [C.POINTER(VuGemmFwd), _i]),
-    "vu_gemm_fwd_workspace_bytes": (_l, [C.POINTER(VuGemmFwd), _i]),
-    "vu_gemm_fwd_bnb_tile": (_l, [C.POINTER(VuGemmFwd), _i]),
-    "vu_gemm_fwd_kernel": (_i, [C.POINTER(VuGemmFwd), _i]),
-    "vu_abi_struct_sizes": (None, [_p]),
-    "vu_bn_bwd_finish": (_i, [_p, _i, _l, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p]),
-    "vu_bn_bwd_finish_workspace_bytes": (_l, [_i, _i]),
-    "vu_gemm_wgrad": (_i, [C.POINTER(VuGemmWgrad), _i, _p]),
-    "vu_gemm_wgrad_tile": (_i, [C.POINTER(VuGemmWgrad), _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "vu_gemm_set_tuning": (_i, [_i, _i]),
-    "vu_gemm_experiment_modes": (_i, []),
-    "vu_slab_reduce": (_i, [_p, _i, _i, _i, _i, _i, _l, _l, _l, _p, _i, _p]),
-    "vu_amax": (_i, [_p, _l, _l, _i, _p, _i, _i, _p]),
-    "vu_quant_fp8": (_i, [_p, _l, _l, _i, _p, _p, _l, _p, _i, _p]),
-    "vu_quant_rows_fp8": (_i, [_p, _i, _l, _p, _l, _p, _p]),
-    "vu_bn_apply_fp8": (_i, [_p, _l, _p, _l, _l, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p]),
-    "vu_conv3x3_fp8_row_tile": (_l, [C.POINTER(VuConvFp8)]),
-    "vu_conv3x3_fp8": (_i, [C.POINTER(VuConvFp8), _p]),
-    "vu_conv3x3_fp8_workspace_bytes": (_l, [C.POINTER(VuConvFp8)]),
-    "vu_conv3x3_fp8_minmax_ok": (_i, [C.POINTER(VuConvFp8)]),
-    "vu_fp8_relu_amax": (_i, [_p, _p, _l, _i, _p, _p, _i, _p, _p]),
-    "vu_permute4_chunk": (_l, []),
-    "vu_permute4_tile": (_l, []),
-    "vu_permute4_batch": (_i, [_p, _i, _l, _p]),
-    "vu_permute4_batch2": (_i, [_p, _i, _i, _l, _l, _p]),
-    "vu_permute4": (_i, [_p, _l, _l, _l, _l, _l, _i, _i, _i, _i, _i, _p, _i, _p]),
-    "vu_bn_finalize": (_i, [_p, _p, _i, _l, _l, _i, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p,
-                            _p, _p, _p]),
-    "vu_bn_finalize_workspace_bytes": (_l, [_i, _i]),
-    "vu_bn_eval_coeffs": (_i, [_p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p]),
-    "vu_bn_apply": (_i, [_p, _l, _p, _l, _l, _i, _p, _p, _i, _i, _p]),
-    "vu_bn_fwd_fused_supported": (_i, [_i, _i, _l, _l, _l]),
-    "vu_bn_bwd_fused_supported": (_i, [_l, _i, _l, _l, _l]),
-    "vu_bn_bwd_fused": (_i, [_p, _l, _p, _l, _l, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _i, _p, _l, _p, _i,
-                             _p]),
-    "vu_bn_fwd_fused": (_i, [_p, _p, _i, _l, _l, _i, _p, _p, _p, _p, _p, _f, _f, _p, _p, _l, _p, _l, _p, _p,
-                             _p, _l, _i, _i, _p]),
-    "vu_bn_bwd_reduce": (_i, [_p, _l, _p, _l, _l, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _i,
-                              _p, _p, _i, _p]),
-    "vu_bn_bwd_apply": (_i, [_p, _l, _p, _l, _l, _i, _p, _p, _p, _p, _i, _p, _l, _i, _p]),
-    "vu_bn_bwd_apply2_ok": (_i, [_i, _l, _l, _l, _l, _l]),
-    "vu_bn_bwd_apply2": (_i, [_p, _l, _p, _l, _p, _l, _l, _i, _p, _p, _p, _p, _p, _l, _p, _l, _i, _p]),
-    "vu_conv_image_wgrad_bn_ok": (_i, [_i, _i, _l, _l, _l, _i, _i, _i, _i]),
-    "vu_conv_image_wgrad_bn_slabs": (_i, [_i, _i, _i]),
-    "vu_conv_image_wgrad_bn": (_i, [_p, _l, _p, _l, _p, _p, _p, _p, _i, _p, _l, _i, _i, _i, _p, _i, _p]),
-    "vu_reduce_workspace_bytes": (_l, [_l, _i]),
-    "vu_chan_sum": (_i, [_p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
-    "vu_copy": (_i, [_p, _l, _i, _p, _l, _i, _l, _i, _i, _p]),
-    "vu_zero": (_i, [_p, _l, _l, _i, _i, _p]),
-    "vu_gpu_delay": (_i, [_i, _p]),
-    "vu_zero_insert2": (_i, [_p, _l, _i, _i, _i, _i, _p, _l, _i, _i, _i, _p]),
-    "vu_input_pack": (_i, [_p, _l, _l, _l, _l, _i, _i, _i, _i, _i, _p, _i, _p]),
-    "vu_maxpool2_fwd": (_i, [_p, _l, _i, _i, _i, _i, _p, _l, _i, _p]),
-    "vu_maxpool2_bwd": (_i, [_p, _l, _p, _l, _i, _i, _i, _i, _p, _l, _p, _l, _i, _p]),
-    "vu_bn_apply_maxpool2": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _p, _i, _i, _p]),
-    "vu_upsample_fwd": (_i, [_p, _l, _i, _i, _i, _i, _p, _l, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "vu_upsample_bwd": (_i, [_p, _l, _i, _i, _i, _i, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i,
-                             _p]),
-    "vu_attn_tile_rows": (_l, []),
-    "vu_attn_psi_fwd": (_i, [_p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
-    "vu_attn_gate_fwd": (_i, [_p, _p, _p, _l, _l, _i, _p, _p, _l, _i, _p]),
-    "vu_attn_gate_bwd": (_i, [_p, _l, _p, _l, _p, _l, _i, _p, _l, _p, _i, _p]),
-    "vu_attn_psi_bwd_workspace_bytes": (_l, [_l, _i]),
-    "vu_attn_psi_bwd_blocks": (_l, [_l]),
-    "vu_attn_psi_bwd_bnb_ok": (_i, [_i]),
-    "vu_attn_psi_bwd_bnb": (_i, [_p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p,
-                                 _i, _p]),
-    "vu_attn_psi_bwd": (_i, [_p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i,
-                             _p]),
-    "vu_attn_tail_bwd_tile": (_l, [_i, _i]),
-    "vu_attn_tail_bwd_ok": (_i, [_l, _i, _i, _l, _l, _l, _l, _l, _l, _i]),
-    "vu_attn_tail_bwd": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _l,
-                              _p, _p, _l, _l, _i, _p, _l, _p, _p, _i, _p]),
-    "vu_pointwise_fwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _l, _i, _p]),
-    "vu_pointwise_bwd_workspace_bytes": (_l, [_l, _i, _i]),
-    "vu_pointwise_bn_fwd": (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _l, _i, _p]),
-    "vu_pointwise_bn_bwd_blocks": (_l, [_l]),
-    "vu_pointwise_bn_bwd": (_i, [_p, _l, _p, _l, _p, _l, _l, _i, _i, _p, _p, _l, _p, _p, _i, _p, _p, _i, _p]),
-    "vu_pointwise_bwd": (_i, [_p, _l, _p, _l, _l, _i, _i, _p, _p, _l, _p, _p, _i, _p, _i, _p]),
-    "vu_loss_workspace_bytes": (_l, []),
-    "vu_bce_dice_fwd2": (_i, [_p, _p, _l, _p, _f, _f, _f, _p, _p, _p, _p]),
-    "vu_bce_dice_bwd": (_i, [_p, _p, _l, _p, _f, _f, _f, _p, _p, _p]),
-    "vu_focal_workspace_bytes": (_l, []),
-    "vu_focal_dice_fwd": (_i, [_p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p]),
-    "vu_focal_dice_bwd": (_i, [_p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p]),
-    "vu_kl_free_bits2": (_i, [_p, _p, _i, _i, _f, _p, _p, _p, _p, _p]),
-    "vu_sumsq": (_i, [_p, _l, _p, _p, _p]),
-    "vu_dice_score": (_i, [_p, _p, _l, _f, _p, _p, _p, _p]),
-    "vu_seg_counts_workspace_bytes": (_l, [_l]),
-    "vu_seg_counts": (_i, [_p, _i, C.POINTER(_l), _i, _i, _p, _i, C.POINTER(_l), _i, _i, _i, _i, _i, _i, _p, _i, _p,
-                           _p, _p]),
-    "vu_seg_metrics": (_i, [_p, _i, _i, C.c_double, _p, _p, _i, _p, _p]),
-    "vu_calib_workspace_bytes": (_l, []),
-    "vu_calib_hist": (_i, [_p, _p, _i, _p, _l, _i, _f, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
-    "vu_calib_metrics": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
-    "vu_mt_chunk_elems": (_l, []),
-    "vu_mt_grad_norm": (_i, [_p, _i, _l, _f, _p, _p, _p, _p]),
-    "vu_mt_scale_grads": (_i, [_p, _i, _l, _p, _p]),
-    "vu_mt_adamw": (_i, [_p, _i, _l, _f, _f, _f, _f, _f, _p, _p]),
-    "vu_mt_adamw_dev": (_i, [_p, _i, _l, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _i,
-                             _p]),
-    "vu_mt_adamw_dev_scaled": (_i, [_p, _i, _l, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p,
-                                    _i, _p, _p]),
-    "vu_maxpool3s2_fwd": (_i, [_p, _l, _i, _i, _i, _i, _p, _l, _p, _i, _p]),
-    "vu_maxpool3s2_bwd": (_i, [_p, _l, _p, _i, _i, _i, _i, _p, _l, _i, _i, _p]),
-    "vu_bn_add_relu": (_i, [_p, _l, _p, _p, _p, _l, _p, _p, _l, _i, _p, _l, _i, _p]),
-    "vu_relu_mask": (_i, [_p, _l, _p, _l, _l, _i, _p, _l, _i, _p]),
-    "vu_sample_sum": (_i, [_p, _l, _i, _i, _i, _f, _p, _i, _p, _i, _p]),
-    "vu_sample_sum_workspace_bytes": (_l, [_i, _i]),
-    "vu_sample_broadcast": (_i, [_p, _i, _i, _i, _f, _p, _l, _i, _i, _p]),
-    "vu_linear_small_fwd": (_i, [_p, _i, _i, _p, _p, _i, _p, _p]),
-    "vu_linear_small_bwd": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _p, _p, _i, _p]),
-    "vu_reparam_fwd": (_i, [_p, _p, _p, _i, _p, _p]),
-    "vu_reparam_bwd": (_i, [_p, _p, _p, _i, _p, _p, _i, _p]),
-    "vu_vae_heads_fwd": (_i, [_p, _l, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
-    "vu_latent_fwd_blocks": (_l, [_i, _i, _i]),
-    "vu_latent_fwd": (_i, [_p, _i, _p, _i, _i, _i, _p]),
-    "vu_latent_part_floats": (_l, [_i, _i]),
-    "vu_latent_bwd_supported": (_i, [_i, _i, _l, _i]),
-    "vu_latent_bwd_sums": (_i, [_p, _i, _i, _i, _p]),
-    "vu_latent_bwd_workspace_bytes": (_l, [_i, _i, _l]),
-    "vu_latent_bwd": (_i, [_p, _i, C.POINTER(VuLatentHeads), _i, _i, _p, _p]),
-    "vu_latent_check_job": (_i, [_i, _i, _l, _i]),
-    "vu_zbias_supported": (_i, [_i, _i, _i]),
-    "vu_zbias_rs_floats": (_l, [_i, _i, _i, _i]),
-    "vu_zbias_fwd": (_i, [_p, _i, _i, _p]),
-    "vu_zbias_bwd": (_i, [_p, _i, _i, _i, _p]),
-    "vu_bn_bwd_apply_zrs_ok": (_i, [_i, _i, _i, _l, _l, _l]),
-    "vu_bn_bwd_apply_zrs": (_i, [_p, _l, _p, _l, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _l, _p, _i, _p]),
-    "vu_mean_groups": (_i, [_p, _i, _l, _p, _p]),
-    "vu_sigmoid": (_i, [_p, _l, _p, _p]),
-    "vu_patch_blend": (_i, [_p, _l, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p]),
-    "vu_blend_finish": (_i, [_p, _p, _l, _p]),
-    "vu_uncertainty": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _p]),
-    "vu_gather_affine": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
-    "vu_patch_stats": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p]),
-    "vu_augment_patch": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, C.c_uint64, C.c_uint32, _p, _p, _p]),
-    "vu_clahe_luts": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p]),
-    "vu_clahe_apply": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
-    "vu_blur_sep": (_i, [_p, _i, _i, _i, _p, _p, _p]),
-}
+# the Vu* struct classes and the VU_* constants are module attributes;
+# _SIGS: name -> (restype, argtypes)
+_STRUCTS, _SIGS, _CONSTS = _load_header()
+globals().update(_STRUCTS)
+globals().update(_CONSTS)
 
 _lib = None
 

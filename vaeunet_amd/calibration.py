@@ -21,9 +21,9 @@ from typing import Optional
 
 import torch
 
-from ._lib import call, ptr, query, stream
+from ._lib import VU_CALIB_NSCALARS, VU_CALIB_RANK_BINS, call, ptr, query, stream
 
-RANK_BINS = 1024      # VU_CALIB_RANK_BINS
+RANK_BINS = VU_CALIB_RANK_BINS
 MAX_CONF_BINS = 64
 SCALAR_NAMES = ("ece", "mce", "brier", "nll", "auroc", "auroc_tie_bound", "auprc", "ause",
                 "n", "positives", "n_uncertainty", "uncertainty_errors")
@@ -140,7 +140,7 @@ def calib_metrics(counts):
         raise RuntimeError("vaeunet_amd metrics run on MI355X (HIP) devices only; calib_metrics got "
                            f"{counts.conf_hist.device}")
     dev = counts.conf_hist.device
-    scalars = torch.empty(len(SCALAR_NAMES), dtype=torch.float64, device=dev)
+    scalars = torch.empty(VU_CALIB_NSCALARS, dtype=torch.float64, device=dev)
     rel = torch.empty((counts.n_bins, 3), dtype=torch.float64, device=dev)
     spars = torch.empty((RANK_BINS + 1, 3), dtype=torch.float64, device=dev)
     call("vu_calib_metrics", ptr(counts.conf_hist), ptr(counts.conf_sum), counts.n_bins, ptr(counts.rank_hist),

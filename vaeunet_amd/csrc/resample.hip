@@ -554,7 +554,7 @@ __global__ __launch_bounds__(256) void permute4_batch_kernel(const VuPermJob* jo
   // 32-bit index math (every weight image has < 2^31 elements)
   const int d[4] = {j.d0, j.d1, j.d2, j.d3};
   const int st[4] = {(int)j.s0, (int)j.s1, (int)j.s2, (int)j.s3};
-  const gfl* in = (const gfl*)(j.in + j.base);
+  const gfl* in = (const gfl*)(j.inp + j.base);
   const uint32_t blk = (uint32_t)(chunk - j.chunk0);
   auto put = [&](uint32_t e, float v) {
     if (j.dtype == VU_BF16) ((gbf*)j.out)[e] = f2bf(v);
@@ -649,7 +649,7 @@ __global__ __launch_bounds__(256) void permute4_tap_kernel(const VuPermJob* jobs
   const VuPermJob& j = jobs[lo];
   const int d[4] = {j.d0, j.d1, j.d2, j.d3};
   const int st[4] = {(int)j.s0, (int)j.s1, (int)j.s2, (int)j.s3};
-  const gfl* in = (const gfl*)(j.in + j.base);
+  const gfl* in = (const gfl*)(j.inp + j.base);
   const uint32_t blk = (uint32_t)(chunk - j.chunk0);
   auto put = [&](uint32_t e, float v) {
     if (j.dtype == VU_BF16) ((gbf*)j.out)[e] = f2bf(v);
