@@ -87,7 +87,7 @@ CONV_CASES = [
     (4, [64, 64], 128, 128, 128),  # BM=128, BN=128 path, two sources
     (2, [24, 8, 16], 6, 6, 40),    # three sources, ragged
     (2, [64, 128], 16, 48, 96),    # bf16 halo kernel: 16x16 tiles, 3 chunks, column tail
-    (2, [128], 8, 64, 192),        # bf16 halo wgrad: 128-row co tiles with a 64-row tail
+    (2, [128], 8, 64, 192),        # bf16 halo wgrad: three 64-row co tiles (small grid: pick_bi answers 64)
     (8, [256], 32, 32, 256),       # small grid: 64-row co tiles (ResNet34 layer3 shape)
     (4, [512], 16, 16, 512),       # 16-pixel-wide halo wgrad tiles (layer4 shape)
 ]
