@@ -12,6 +12,9 @@ build/%.o: vaeunet_amd/csrc/%.hip $(wildcard vaeunet_amd/csrc/*.h) include/vaeun
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
+# the median's window must stay in registers: print its scratch / spill / VGPR / LDS figures
+build/median.o: FLAGS += -Rpass-analysis=kernel-resource-usage
+
 $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJ) -o $@
 

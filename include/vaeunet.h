@@ -1159,6 +1159,33 @@ int vu_clahe_apply(const float* img, int B, int H, int W, const float* clip,
 int vu_blur_sep(const float* img, int B, int H, int W, const float* table,
                 float* out, void* stream);
 
+/* Median blur of an image batch img [B][H][W][3] (NHWC fp32) -> out of the
+ * same shape (this project's own definition, unpinned against
+ * albumentations / OpenCV; like cv2.medianBlur it takes odd square windows,
+ * works per channel and replicates the border).  In the patch loader it runs
+ * after the blur and ahead of vu_augment_patch: CLAHE, blur, median, warp.
+ *   radius  [B] fp32 (device), one per sample; the kernel uses r =
+ *           (int)fminf(fmaxf(radius[b], 0), VU_MEDIAN_RMAX) (a NaN gives 0);
+ *           the window is (2r + 1) x (2r + 1), r = 0 switches the sample off:
+ *           its output is its input bitwise
+ *   window  per pixel and channel, the (2r + 1)^2 values at the coordinates
+ *           clamped to [0, H - 1] x [0, W - 1] (replicate)
+ *   order   the bits u of a value sort by key = (u >> 31) ? ~u : u | 0x80000000
+ *           compared as uint32: a total order, the ordinary one on finite
+ *           floats, -0 below +0, NaNs with a clear sign bit above +inf and
+ *           NaNs with a set sign bit below -inf
+ *   out     the window element of rank ((2r + 1)^2 - 1) / 2 in ascending key
+ *           order: bitwise one of the window's inputs, NaN payloads included
+ *           (on finite values the median of the window)
+ * A pixel's result depends on its sample and position only, not on B, on other
+ * samples' radii or on the launch geometry.
+ * hipErrorInvalidValue, nothing launched: a negative size, then (B, H and W
+ * all > 0) a null pointer, out == img (the halo reads make in-place wrong),
+ * B > 65535, H or W > 32768.  B, H or W == 0 returns 0, nothing launched. */
+#define VU_MEDIAN_RMAX 3
+int vu_median_blur(const float* img, int B, int H, int W, const float* radius,
+                   float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

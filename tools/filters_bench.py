@@ -5,6 +5,10 @@ image 8x3x512x512 fp32 channels_last (mask 8x1x512x512 for the vu_augment_patch 
   (t1) (t3) (t7) the same blur composed from torch ops: reflect pad + depthwise conv2d, per axis
   (p)  the three stages: CLAHE -> blur r = 3 -> vu_augment_patch with identity parameters
   (a0) vu_augment_patch with identity parameters alone: the streaming yardstick of §4.8
+  (m1) (m2) (m3) vu_median_blur at r = 1, 2, 3; (b0) copies the same bytes
+  (tm) the r = 3 median composed from torch ops: replicate pad + unfold + median over the 49 taps, on ONE sample
+       (1x3x512x512: the unfolded batch would be 1.2 GB), 1 / 50 of the iterations; compare 8 x its time
+  (pm) the four stages: CLAHE -> blur r = 3 -> median r = 3 -> vu_augment_patch with identity parameters
 Two figures per variant, both stream time per batch between hip events around
 `iters` back-to-back runs, `rounds` times with the variants alternating:
 `eager` (Python and the launches included) and `graph` (captured with
@@ -62,6 +66,14 @@ def torch_blur(img, kh, kv, r):
     return F.conv2d(F.pad(v, (0, 0, r, r), mode="reflect"), kv, groups=3)
 
 
+def torch_median(img, r):
+    """replicate pad + unfold of the (2r + 1)^2 taps + median over them (odd count: the middle element)"""
+    k = 2 * r + 1
+    n, c, h, w = img.shape
+    taps = F.unfold(F.pad(img, (r, r, r, r), mode="replicate"), k).view(n, c, k * k, h, w)
+    return taps.median(dim=2).values
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=500)
@@ -92,6 +104,13 @@ def main():
     def apply_only():
         K.call("vu_clahe_apply", K.ptr(img), B, H, W, K.ptr(clip), *TILES, K.ptr(luts), K.ptr(out), K.stream())
 
+    mrad = {r: torch.full((B,), float(r), device=dev) for r in (1, 2, 3)}
+    one = img[:1].contiguous()          # NCHW: what unfold wants
+
+    def pipeline_median():
+        v = D._launch_median(D._launch_blur(D._launch_clahe(img, clip, TILES), tabs[3]), mrad[3])
+        return D._launch_augment(v, msk, ip, ikx, iky, 1, 0, 1)
+
     def pipeline():
         v = D._launch_blur(D._launch_clahe(img, clip, TILES), tabs[3])
         return D._launch_augment(v, msk, ip, ikx, iky, 1, 0, 1)
@@ -109,7 +128,17 @@ def main():
                 ("t7 torch pad + depthwise conv2d, r = 7  ", lambda: torch_blur(img, *kern[7], 7), 2 * nimg),
                 ("p  CLAHE -> blur r = 3 -> augment (ident)", pipeline, 5 * nimg + 32 * B * H * W),
                 ("a0 vu_augment_patch, identity params    ", lambda: D._launch_augment(img, msk, ip, ikx, iky, 1, 0, 1),
-                 32 * B * H * W)]
+                 32 * B * H * W),
+                ("m1 vu_median_blur r = 1                 ", lambda: D._launch_median(img, mrad[1]), 2 * nimg),
+                ("m2 vu_median_blur r = 2                 ", lambda: D._launch_median(img, mrad[2]), 2 * nimg),
+                ("m3 vu_median_blur r = 3                 ", lambda: D._launch_median(img, mrad[3]), 2 * nimg),
+                ("tm torch pad + unfold + median, r = 3, 1 sample", lambda: torch_median(one, 3), 2 * nimg // B),
+                ("pm CLAHE -> blur 3 -> median 3 -> augment", pipeline_median, 7 * nimg + 32 * B * H * W)]
+    slow = {"tm torch pad + unfold + median, r = 3, 1 sample": 50}     # name -> divisor of --iters
+    same = torch.equal(D._launch_median(img[:1], mrad[3][:1]), torch_median(one, 3).contiguous(
+        memory_format=torch.channels_last))
+    print(f"vu_median_blur vs the torch composition at r = 3 (one sample): {'bitwise equal' if same else 'DIFFERENT'}",
+          flush=True)
     # the two blurs are the same filter: compare them once
     for r in (1, 3, 7):
         d = float((D._launch_blur(img, tabs[r]) - torch_blur(img, *kern[r], r)).abs().max())
@@ -125,8 +154,9 @@ def main():
     gtimes = {name: [] for name, _, _ in variants}
     for _ in range(a.rounds):
         for (name, fn, _), rep in zip(variants, replays):
-            times[name].append(stream_us(fn, a.iters))
-            gtimes[name].append(stream_us(rep, a.iters))
+            n = max(1, a.iters // slow.get(name, 1))
+            times[name].append(stream_us(fn, n))
+            gtimes[name].append(stream_us(rep, n))
     print(f"image {B}x3x{H}x{W} ({nimg / 1e6:.1f} MB)  ({a.iters} batches per figure, {a.rounds} rounds)", flush=True)
     for name, _, nbytes in variants:
         v, w = sorted(times[name]), sorted(gtimes[name])

@@ -41,8 +41,11 @@ blend of four lookup tables) and blur (``blur``: a separable symmetric kernel
 of radius <= 7, Gaussian or box rows from ``blur_weights``) are launches of
 their own ahead of that one, so both see the un-warped patch
 and the noise stays white; ``TrainAugment(p_clahe=, p_blur=)`` draws them per
-sample.  Their definitions are this project's too; the LAB-space CLAHE and
-MedianBlur are not built.
+sample.  The median blur (``median_blur``: per channel, window 3, 5 or 7 per
+sample, replicated border) is one more launch between the blur
+and the warp, bitwise a selection of its inputs; ``TrainAugment(p_median=)``
+draws it.  Their definitions are this project's too; the LAB-space CLAHE is
+not built.
 Normalize(mean=0, std=1) of train.py:37 is the identity.
 """
 import logging
@@ -55,7 +58,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from ._lib import F32
+from ._lib import F32, VU_MEDIAN_RMAX
 
 CL = torch.channels_last
 
@@ -264,6 +267,7 @@ MAX_GRID_STEPS = 32
 RMAX = 7                          # largest blur radius
 NBLUR = 2 + RMAX                  # a blur row: r, w_0..w_RMAX
 MAX_TILES = 16                    # CLAHE tiles per axis
+MEDIAN_RMAX = VU_MEDIAN_RMAX      # largest median radius: window 7
 BORDERS = {"constant": 0, "reflect101": 1}
 
 _GREY = np.array([0.299, 0.587, 0.114])
@@ -375,13 +379,15 @@ class TrainAugment:
     border     'reflect101' or 'constant'
     filters    (ahead of the warp, image only; off by default)
                p_clahe with the clahe_clip range and clahe_tiles (rows,
-               columns); p_blur with the blur_sigma range of a Gaussian"""
+               columns); p_blur with the blur_sigma range of a Gaussian;
+               p_median with median_limit, the largest odd window (3, 5 or 7;
+               DESIGN.md §4.10)"""
 
     def __init__(self, p_hflip=0.5, p_vflip=0.5, p_rot90=0.5, p_affine=0.5, rotate_limit=15.0, scale_limit=0.1,
                  shift_limit=0.0625, p_grid=0.3, grid_steps=5, grid_limit=0.3, p_gamma=0.3, gamma_range=(0.8, 1.25),
                  p_colour=0.5, brightness_limit=0.2, contrast_limit=0.2, saturation_limit=0.2, hue_limit=0.02,
                  p_noise=0.3, noise_sigma=(0.005, 0.03), border="reflect101", p_clahe=0.0, clahe_clip=(1.0, 4.0),
-                 clahe_tiles=(8, 8), p_blur=0.0, blur_sigma=(0.5, 1.5)):
+                 clahe_tiles=(8, 8), p_blur=0.0, blur_sigma=(0.5, 1.5), p_median=0.0, median_limit=7):
         if border not in BORDERS:
             raise ValueError(f"border must be one of {sorted(BORDERS)}, got {border!r}")
         if not 1 <= int(grid_steps) <= MAX_GRID_STEPS:
@@ -405,6 +411,10 @@ class TrainAugment:
         self.clahe_tiles = _check_tiles(clahe_tiles)
         self.p_clahe, self.clahe_clip = p_clahe, tuple(clahe_clip)
         self.p_blur, self.blur_sigma = p_blur, tuple(blur_sigma)
+        if isinstance(median_limit, bool) or not isinstance(median_limit, (int, np.integer)) \
+                or median_limit % 2 == 0 or not 3 <= median_limit <= 2 * MEDIAN_RMAX + 1:
+            raise ValueError(f"median_limit must be an odd window in [3, {2 * MEDIAN_RMAX + 1}], got {median_limit!r}")
+        self.p_median, self.median_limit = p_median, int(median_limit)
 
     def _knots(self, size, S, rng):
         w = 1.0 + rng.uniform(-self.grid_limit, self.grid_limit, S)
@@ -459,6 +469,18 @@ class TrainAugment:
             if rng.random() < self.p_blur:
                 table[b] = blur_weights(sigma=rng.uniform(*self.blur_sigma))
         return clip, table
+
+    def draw_median(self, B, rng):
+        """Host array radius [B] fp32 of the median blur for one batch: one coin
+        per sample; on success the window is uniform over the odd values
+        3..median_limit and the radius (window - 1) / 2, else 0 (off).
+        PatchCache calls it after ``draw`` and ``draw_filters``, and only when
+        p_median is positive, so their sequences are what they were."""
+        radius = np.zeros(B, np.float32)
+        for b in range(B):
+            if rng.random() < self.p_median:
+                radius[b] = int(rng.integers(1, (self.median_limit - 1) // 2 + 1))
+        return radius
 
 
 def _check_augment_args(img, msk, params, gx, gy, seed, offset, border):
@@ -536,6 +558,26 @@ def _check_filter_args(img, clip=None, tiles=(8, 8), table=None):
     return clip, tiles, table
 
 
+def _check_median_args(img, radius):
+    """Host validation of a median blur call on image [B, 3, H, W]; returns the
+    radius as a contiguous fp32 numpy array [B].  Nothing here touches a device."""
+    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
+        raise ValueError(f"expected image [B, 3, H >= 1, W >= 1], got {tuple(img.shape)}")
+    if img.dtype != torch.float32:
+        raise ValueError("image must be float32")
+    B = img.shape[0]
+    try:
+        radius = np.asarray(radius, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"the median radius must be a number or [{B}] numbers, got {radius!r}") from None
+    radius = np.broadcast_to(radius, (B,)) if radius.ndim == 0 else radius
+    if radius.shape != (B,):
+        raise ValueError(f"the median radius must be a scalar or [{B}], got {radius.shape}")
+    if not (np.isfinite(radius) & (radius == np.round(radius)) & (radius >= 0) & (radius <= MEDIAN_RMAX)).all():
+        raise ValueError(f"every median radius must be an integer in [0, {MEDIAN_RMAX}] (0 switches the sample off)")
+    return np.ascontiguousarray(radius, dtype=np.float32)
+
+
 def _launch_clahe(img, dclip, tiles):
     """vu_clahe_luts + vu_clahe_apply on device tensors"""
     img = img.contiguous(memory_format=CL)
@@ -556,6 +598,16 @@ def _launch_blur(img, dtable):
     out = K.empty_act(B, 3, H, W, torch.float32, img.device)
     with torch.cuda.device(img.device):
         K.call("vu_blur_sep", K.ptr(img), B, H, W, K.ptr(dtable), K.ptr(out), K.stream())
+    return out
+
+
+def _launch_median(img, dradius):
+    """The one vu_median_blur launch on device tensors"""
+    img = img.contiguous(memory_format=CL)
+    B, _, H, W = img.shape
+    out = K.empty_act(B, 3, H, W, torch.float32, img.device)
+    with torch.cuda.device(img.device):
+        K.call("vu_median_blur", K.ptr(img), B, H, W, K.ptr(dradius), K.ptr(out), K.stream())
     return out
 
 
@@ -586,6 +638,17 @@ def blur(image, table):
     return _launch_blur(image, torch.from_numpy(table).to(image.device))
 
 
+def median_blur(image, radius):
+    """Median blur of image [B, 3, H, W] (fp32 on the device), per channel, over
+    the (2r + 1) x (2r + 1) window with a replicated border.
+    ``radius``: an integer in 0..3 or one per sample ([B]); 0 = off (the sample
+    comes back bitwise).  Every output value is bitwise one of its window's
+    inputs.  Returns channels_last.  Checked on the host first (ValueError)."""
+    radius = _check_median_args(image, radius)
+    _need_device(image, "median_blur")
+    return _launch_median(image, torch.from_numpy(radius).to(image.device))
+
+
 def _launch_augment(img, msk, dparams, dgx, dgy, seed, offset, border):
     """The one vu_augment_patch launch on device tensors (border: the C code)."""
     img = img.contiguous(memory_format=CL)
@@ -601,7 +664,7 @@ def _launch_augment(img, msk, dparams, dgx, dgy, seed, offset, border):
 
 
 def augment_patches(img, msk, params, gx, gy, seed, offset=0, border="reflect101", clahe_clip=None,
-                    clahe_tiles=(8, 8), blur=None):
+                    clahe_tiles=(8, 8), blur=None, median=None):
     """Augment image [B, 3, H, W] and mask [B, Cm, H, W] (fp32 on the device) in
     ONE launch (vu_augment_patch) with the host arrays of
     ``TrainAugment.draw`` (or any of the same layout); returns (image, mask),
@@ -611,15 +674,18 @@ def augment_patches(img, msk, params, gx, gy, seed, offset=0, border="reflect101
     function of (seed, offset, sample, pixel) alone.  ``clahe_clip`` (scalar or
     [B], with ``clahe_tiles``) and ``blur`` ([B, 9]), the arrays of
     ``TrainAugment.draw_filters``, run CLAHE and / or the blur on the image
-    ahead of that launch; their tables ride in the same
-    upload."""
+    ahead of that launch; ``median`` (a radius 0..3, scalar or
+    [B], the array of ``TrainAugment.draw_median``) runs the median blur after
+    them: CLAHE -> blur -> median -> warp.  Their tables ride
+    in the same upload."""
     params, gx, gy = _check_augment_args(img, msk, params, gx, gy, seed, offset, border)
     clip, tiles, table = _check_filter_args(img, clahe_clip, clahe_tiles, blur)
+    radius = None if median is None else _check_median_args(img, median)
     if img.device.type != "cuda" or msk.device != img.device:
         raise RuntimeError(f"augment_patches runs on MI355X (HIP) devices only; got {img.device} and {msk.device}")
     B, S1 = params.shape[0], gx.shape[1]
     parts = [params.reshape(-1), gx.reshape(-1), gy.reshape(-1)]
-    parts += [a.reshape(-1) for a in (clip, table) if a is not None]
+    parts += [a.reshape(-1) for a in (clip, table, radius) if a is not None]
     dev = torch.from_numpy(np.concatenate(parts)).to(img.device)      # one upload for every table
     n0, n1 = B * NPARAM, B * S1
     n2 = n0 + 2 * n1
@@ -627,7 +693,10 @@ def augment_patches(img, msk, params, gx, gy, seed, offset=0, border="reflect101
         img = _launch_clahe(img, dev[n2:n2 + B], tiles)
         n2 += B
     if table is not None:
-        img = _launch_blur(img, dev[n2:].view(B, NBLUR))
+        img = _launch_blur(img, dev[n2:n2 + B * NBLUR].view(B, NBLUR))
+        n2 += B * NBLUR
+    if radius is not None:
+        img = _launch_median(img, dev[n2:n2 + B])
     return _launch_augment(img, msk, dev[:n0].view(B, NPARAM), dev[n0:n0 + n1].view(B, S1),
                            dev[n0 + n1:n0 + 2 * n1].view(B, S1), seed, offset, BORDERS[border])
 
@@ -644,8 +713,9 @@ class PatchCache:
     batches augmented so far; the batch gains ``aug_params``, what
     ``augment_patches`` needs to replay it; with ``p_clahe`` / ``p_blur``
     positive the CLAHE and blur launches run first and their drawn arrays
-    join ``aug_params``).  All draws come from the generator seeded with
-    ``seed``."""
+    join ``aug_params``; with ``p_median`` positive the median blur follows
+    them and ``aug_params`` gains ``median``).  All draws come from the
+    generator seeded with ``seed``."""
 
     def __init__(self, paths, batch_size, device="cuda", augment=False, shuffle=False, seed=0, workers=6,
                  drop_last=False):
@@ -731,6 +801,8 @@ class PatchCache:
                         aug["clahe_clip"], aug["clahe_tiles"] = clip, self.augment.clahe_tiles
                     if self.augment.p_blur > 0:
                         aug["blur"] = table
+                if self.augment.p_median > 0:
+                    aug["median"] = self.augment.draw_median(img.shape[0], self.rng)
                 img, msk = augment_patches(img, msk, **aug)
                 self.aug_calls += 1
                 extra["aug_params"] = aug

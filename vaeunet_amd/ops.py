@@ -36,6 +36,8 @@ Reference ops each one replaces:
                                  colour, noise; DESIGN.md §4.8's definitions) as one launch per batch
   clahe / blur_separable         the CLAHE and Blur / GaussianBlur steps of that transform (DESIGN.md §4.9's
                                  definitions; integer-luma CLAHE, separable kernel of radius <= 7)
+  median_blur                    its MedianBlur step (DESIGN.md §4.10's definition; window 3, 5 or 7 per sample,
+                                 bitwise a selection of the inputs)
 """
 import ctypes as C
 import types
@@ -818,7 +820,32 @@ def _(image, table):
     return _cl_empty(*image.shape, image)
 
 
+# ---- median blur -----------------------------------------------------------------------------
+def _median_check(image, radius):
+    _filter_check(image, "median_blur")
+    if tuple(radius.shape) != (image.shape[0],) or radius.dtype != torch.float32 or image.dtype != torch.float32:
+        raise ValueError("vaeunet::median_blur: radius must be [B] and both tensors float32")
+
+
+@torch.library.custom_op(f"{_NS}::median_blur", mutates_args=(), device_types="cuda")
+def median_blur(image: torch.Tensor, radius: torch.Tensor) -> torch.Tensor:
+    """vaeunet_amd.data.median_blur on a device table: image [B, 3, H, W] fp32,
+    radius [B] fp32 on the device (the kernel clamps it to 0..3 and takes a NaN
+    as 0 = off; NOT validated here, use data.median_blur for host values),
+    window 2r + 1 per channel, replicated border.  Returns
+    channels_last.  Not differentiable (a selection; a data transform)."""
+    _median_check(image, radius)
+    return _data._launch_median(image, radius.contiguous())
+
+
+@median_blur.register_fake
+def _(image, radius):
+    _median_check(image, radius)
+    return _cl_empty(*image.shape, image)
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
-       "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch", "clahe", "blur_separable")
+       "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch", "clahe", "blur_separable",
+       "median_blur")
