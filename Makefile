@@ -14,6 +14,8 @@ build/%.o: vaeunet_amd/csrc/%.hip $(wildcard vaeunet_amd/csrc/*.h) include/vaeun
 
 # the median's window must stay in registers: print its scratch / spill / VGPR / LDS figures
 build/median.o: FLAGS += -Rpass-analysis=kernel-resource-usage
+# the labelling tile kernel must not use scratch
+build/ccl.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 
 $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJ) -o $@

@@ -1186,6 +1186,89 @@ int vu_blur_sep(const float* img, int B, int H, int W, const float* table,
 int vu_median_blur(const float* img, int B, int H, int W, const float* radius,
                    float* out, void* stream);
 
+/* ---- lesion-level evaluation: component labelling, matching, FROC -------- */
+/* DESIGN.md 4.11; this project's own definitions, unpinned against any
+ * reference code.
+ *
+ * Plane: one slice [H][W] of a contiguous [planes][H][W] tensor (planes = B C);
+ * planes never interact.  Foreground: a VU_CCL_U8 element is foreground when it
+ * is nonzero, a VU_CCL_F32 element p when p > threshold, strictly (a NaN is
+ * background).  Connectivity is 8 or 4.
+ *
+ * Label (int32): background 0; a foreground pixel gets 1 + the smallest
+ * row-major index y W + x of any pixel of its component.  The label is
+ * canonical: it does not depend on the tiling, the launch order or the outcome
+ * of any atomic, two runs are bitwise equal, and a labelling from any algorithm
+ * maps onto it exactly.  H W <= VU_CCL_MAX_PLANE = 2^31 - 2.  ncomp (optional,
+ * int64 per plane) receives the number of components.  Labels are not
+ * renumbered 1..K: every per-component table is an image indexed by the root
+ * pixel, label - 1.
+ *
+ * Component tables.  Area: the pixel count of a component.  Score of a
+ * prediction component ("candidate"): the maximum over its pixels of the fp32
+ * input, a negative value or -0 counting as 0; 1.0 for a VU_CCL_U8 input.  Kept
+ * candidates: those with area >= min_area (>= 1); a dropped candidate is
+ * neither a true nor a false positive and detects nothing.
+ *
+ * Matching, any-overlap rule.  A kept candidate is a false positive when none
+ * of its pixels is ground-truth foreground.  A ground-truth component is
+ * detected when at least one of its pixels belongs to a kept candidate; its
+ * score is then the largest score among the kept candidates that overlap it.
+ * counts [planes][4] int64 = (n_gt, n_gt_detected, n_pred kept, n_pred_fp),
+ * overwritten.
+ *
+ * FROC.  A score s falls into bin t >= nb ? nb - 1 : (int)t with t = s * nb in
+ * fp32, i.e. min(nb - 1, (int)(s nb)); 1 <= nb <= VU_FROC_MAX_BINS.  hist_fp[nb]
+ * counts the false-positive candidates and hist_gt[nb] the detected
+ * ground-truth components; both are int64 and vu_lesion_match ADDS to them
+ * (both null: no histograms).  Operating point k keeps the scores in bins >= k:
+ *   sens[k] = sum_{b >= k} hist_gt[b] / n_gt
+ *   fppi[k] = sum_{b >= k} hist_fp[b] / n_planes           (fp64 quotients)
+ * with n_gt = the sum of column 0 of the `rows` rows of a counts table.  The
+ * FROC score is the mean of the sensitivities at fppi <= 1/8, 1/4, 1/2, 1, 2, 4
+ * and 8 (the Retinopathy Online Challenge convention): each term is the largest
+ * sens[k] among the points with fppi[k] <= target -- both fall with k, so that
+ * is sens at the first such k -- and 0 when there is none; no interpolation;
+ * the seven terms are summed in that order in fp64 and divided by 7.  With
+ * n_gt == 0 every sensitivity, and the score, is NaN.
+ *
+ * vu_lesion_metrics: out[3] fp32 from the column sums of a counts table:
+ * sensitivity (n_gt_detected + eps) / (n_gt + eps), precision
+ * (n_pred - n_pred_fp + eps) / (n_pred + eps) -- fp64 from the integers,
+ * rounded once, the eps convention of vu_seg_metrics -- and false positives per
+ * plane n_pred_fp / n_planes.
+ *
+ * workspace: vu_ccl_workspace_bytes(planes, H, W) bytes (-1 for sizes that are
+ * refused).  vu_ccl_label needs none: the label image is its own union-find.
+ * vu_ccl_remove_small writes mask (uint8: 1 where the pixel's component has
+ * area >= min_area) and / or areas (int32: the area at every foreground pixel,
+ * 0 on the background) from a label image; at least one of the two.
+ *
+ * hipErrorInvalidValue, nothing launched: a negative size, H W above
+ * VU_CCL_MAX_PLANE, an unknown dtype or connectivity, min_area < 1, nb outside
+ * its range, then (no size zero) a null pointer.  A size of zero returns 0. */
+#define VU_CCL_U8 0
+#define VU_CCL_F32 1
+#define VU_CCL_MAX_PLANE 2147483646
+#define VU_FROC_MAX_BINS 1048576
+int64_t vu_ccl_workspace_bytes(int64_t planes, int H, int W);
+int vu_ccl_label(const void* x, int dtype, float threshold, int64_t planes,
+                 int H, int W, int connectivity, int32_t* labels,
+                 int64_t* ncomp, void* stream);
+int vu_ccl_remove_small(const int32_t* labels, int64_t planes, int H, int W,
+                        int min_area, uint8_t* mask, int32_t* areas,
+                        void* workspace, void* stream);
+int vu_lesion_match(const int32_t* pred_labels, const int32_t* gt_labels,
+                    const void* pred, int dtype, int64_t planes, int H, int W,
+                    int min_area, int nb, int64_t* counts, int64_t* hist_fp,
+                    int64_t* hist_gt, void* workspace, void* stream);
+int vu_lesion_metrics(const int64_t* counts, int64_t rows, int64_t n_planes,
+                      double eps, float* out, void* stream);
+int vu_froc_metrics(const int64_t* hist_fp, const int64_t* hist_gt,
+                    const int64_t* counts, int64_t rows, int64_t n_planes,
+                    int nb, double* sens, double* fppi, double* score,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ line away):
 """
 import torch
 
+from .lesions import LESION_METRIC_NAMES
 from .metrics import METRIC_NAMES, SegmentationMeter
 
 CL = torch.channels_last
@@ -30,7 +31,6 @@ def _split_batch(batch):
     return image, mask
 
 
-@torch.inference_mode()
 def evaluate(net, dataloader, device, amp=True, align_corners=False, max_batches=None):
     """Validate ``net`` over ``dataloader``; returns a dict of Python floats:
     ``dice, iou, precision, recall, specificity, accuracy`` (mean over batches
@@ -43,6 +43,26 @@ def evaluate(net, dataloader, device, amp=True, align_corners=False, max_batches
     ([B, H, W]) gets one.  The logits are resized to the mask's resolution
     inside the metric kernel when the two differ.  The net's training mode is
     restored on return."""
+    return _evaluate(net, dataloader, device, amp, align_corners, max_batches, None)
+
+
+def evaluate_with_lesions(net, dataloader, device, lesion_meter, amp=True, align_corners=False, max_batches=None):
+    """``evaluate`` plus lesion-level scores.  lesion_meter: a
+    ``lesions.LesionMeter`` (not reset here).  Each batch's hard prediction at
+    mask resolution -- written by the counts pass -- and its mask go to
+    ``lesion_meter.update``, and the result gains ``lesion_sensitivity``,
+    ``lesion_precision``, ``lesion_fp_per_image`` (floats) and ``lesion_n_gt``,
+    ``lesion_n_pred`` (ints) of the meter's totals, read in the same single
+    transfer as the pixel scores."""
+    if lesion_meter is None:
+        raise ValueError("evaluate_with_lesions: lesion_meter is required (evaluate() is the loop without one)")
+    return _evaluate(net, dataloader, device, amp, align_corners, max_batches, lesion_meter)
+
+
+@torch.inference_mode()
+def _evaluate(net, dataloader, device, amp, align_corners, max_batches, lesion_meter):
+    """the loop of both; with lesion_meter None the launches, the result keys and the one synchronisation are those
+    of evaluate() before the lesion scores existed"""
     device = torch.device(device)
     was_training = net.training
     net.eval()
@@ -61,14 +81,38 @@ def evaluate(net, dataloader, device, amp=True, align_corners=False, max_batches
             with torch.autocast(device.type, dtype=torch.bfloat16, enabled=bool(amp)):
                 out = net(image)
             logits = out[0] if isinstance(out, (tuple, list)) else out
-            meter.update(logits, mask)
+            if lesion_meter is None:
+                meter.update(logits, mask)
+            else:
+                hard = torch.empty(mask.shape, dtype=torch.uint8, device=device)
+                meter.update(logits, mask, hard_mask=hard)
+                lesion_meter.update(hard, mask)
     finally:
         net.train(was_training)
     if meter.batches == 0:
         raise ValueError("evaluate: the dataloader produced no batch")
+    if lesion_meter is not None:
+        return _with_lesions(meter, lesion_meter)
     # one transfer (and the only host synchronisation) for all twelve numbers
     both = torch.stack([meter.values("batch_mean"), meter.values("pooled")]).cpu()
     res = {k: both[0, i].item() for i, k in enumerate(METRIC_NAMES)}
     res.update({f"pooled_{k}": both[1, i].item() for i, k in enumerate(METRIC_NAMES)})
     res["batches"] = meter.batches
+    return res
+
+
+def _with_lesions(meter, lesion_meter):
+    """the result dict with the lesion keys: all numbers in one fp64 transfer (fp32 values and counts below 2^53
+    pass through fp64 unchanged)"""
+    k = len(METRIC_NAMES)
+    totals = lesion_meter.counts().sum(0)
+    flat = torch.cat([meter.values("batch_mean").double(), meter.values("pooled").double(),
+                      lesion_meter.values().double(), totals.double()]).cpu()
+    res = {name: flat[i].item() for i, name in enumerate(METRIC_NAMES)}
+    res.update({f"pooled_{name}": flat[k + i].item() for i, name in enumerate(METRIC_NAMES)})
+    res["batches"] = meter.batches
+    for i, name in enumerate(LESION_METRIC_NAMES):
+        res[f"lesion_{name}"] = flat[2 * k + i].item()
+    res["lesion_n_gt"] = int(flat[2 * k + 3].item())
+    res["lesion_n_pred"] = int(flat[2 * k + 5].item())
     return res

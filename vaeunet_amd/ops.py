@@ -38,6 +38,8 @@ Reference ops each one replaces:
                                  definitions; integer-luma CLAHE, separable kernel of radius <= 7)
   median_blur                    its MedianBlur step (DESIGN.md §4.10's definition; window 3, 5 or 7 per sample,
                                  bitwise a selection of the inputs)
+  label_components /             connected-component labels per (image, class) plane and the removal of small
+  remove_small_components        components (DESIGN.md §4.11's definitions; canonical labels = 1 + first raster pixel)
 """
 import ctypes as C
 import types
@@ -49,6 +51,7 @@ from . import engine as E
 from . import kernels as K
 from . import calibration as _calibration
 from . import data as _data
+from . import lesions as _lesions
 from . import metrics as _metrics
 from ._lib import call, ptr, query, stream
 from .engine import conv_layout, convT_layout, w3x3_dgrad, w3x3_fwd, wT_dgrad, wT_fwd
@@ -844,8 +847,45 @@ def _(image, radius):
     return _cl_empty(*image.shape, image)
 
 
+# ---- connected components ----------------------------------------------------------------------
+def _ccl_check(x, connectivity, threshold, what):
+    _lesions._check_connectivity(connectivity, f"vaeunet::{what}")
+    _lesions._check_input(x, threshold, f"vaeunet::{what}")
+
+
+@torch.library.custom_op(f"{_NS}::label_components", mutates_args=(), device_types="cuda")
+def label_components(x: torch.Tensor, connectivity: int = 8, threshold: Optional[float] = None) -> torch.Tensor:
+    """vaeunet_amd.lesions.label_components: x [B, C, H, W] uint8 / bool (nonzero
+    is foreground) or float32 (x > threshold) -> int32 labels, 0 on the
+    background, else 1 + the smallest row-major index of the pixel's component
+    (DESIGN.md §4.11).  Not differentiable."""
+    return _lesions.label_components(x, connectivity, threshold)
+
+
+@label_components.register_fake
+def _(x, connectivity=8, threshold=None):
+    _ccl_check(x, connectivity, threshold, "label_components")
+    return torch.empty(x.shape, dtype=torch.int32, device=x.device)
+
+
+@torch.library.custom_op(f"{_NS}::remove_small_components", mutates_args=(), device_types="cuda")
+def remove_small_components(x: torch.Tensor, min_area: int, connectivity: int = 8,
+                            threshold: Optional[float] = None) -> torch.Tensor:
+    """vaeunet_amd.lesions.remove_small_components: uint8 [B, C, H, W], 1 on the
+    foreground pixels of x whose component has at least min_area pixels
+    (DESIGN.md §4.11).  Not differentiable."""
+    return _lesions.remove_small_components(x, min_area, connectivity, threshold)
+
+
+@remove_small_components.register_fake
+def _(x, min_area, connectivity=8, threshold=None):
+    _lesions._check_min_area(min_area, "vaeunet::remove_small_components")
+    _ccl_check(x, connectivity, threshold, "remove_small_components")
+    return torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
        "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch", "clahe", "blur_separable",
-       "median_blur")
+       "median_blur", "label_components", "remove_small_components")
