@@ -16,6 +16,8 @@ build/%.o: vaeunet_amd/csrc/%.hip $(wildcard vaeunet_amd/csrc/*.h) include/vaeun
 build/median.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 # the labelling tile kernel must not use scratch
 build/ccl.o: FLAGS += -Rpass-analysis=kernel-resource-usage
+# the distance transform's passes must not use scratch
+build/edt.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 
 $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJ) -o $@

@@ -1269,6 +1269,75 @@ int vu_froc_metrics(const int64_t* hist_fp, const int64_t* hist_gt,
                     int nb, double* sens, double* fppi, double* score,
                     void* stream);
 
+/* ---- boundary metrics: distance transform, HD, HD95, ASSD, surface Dice --- */
+/* DESIGN.md 4.12; this project's own definitions, unpinned against any
+ * reference code.
+ *
+ * Planes and foreground are those of the lesion-level evaluation above: a
+ * VU_CCL_U8 element is foreground when nonzero, a VU_CCL_F32 element p when
+ * p > threshold, strictly (a NaN is background).  vu_surface_stats reads its
+ * ground truth with the threshold 0.5 (nonzero for VU_CCL_U8).
+ *
+ * Boundary pixel: a foreground pixel with at least one of its four neighbours
+ * background or outside the plane, i.e. A & ~erosion(A) with the cross element
+ * and a zero border.  vu_edt_boundary writes it as uint8 0 / 1.
+ *
+ * Squared distance transform: int32 dist2[y][x] = the minimum over the sites
+ * (y', x') of (y - y')^2 + (x - x')^2, exact.  mode selects the sites: the
+ * foreground pixels (VU_EDT_TO_FOREGROUND), the background pixels
+ * (VU_EDT_TO_BACKGROUND; scipy.ndimage.distance_transform_edt's convention) or
+ * the boundary pixels (VU_EDT_TO_BOUNDARY).  A plane without a site is
+ * VU_EDT_INF = 2^31 - 1 everywhere.  H, W <= VU_EDT_MAX_DIM = 16384, so a real
+ * distance is <= 2^29 and neither overflows nor meets the sentinel.  With
+ * out_f32 = 1 the output is float32 (float)sqrt((double)dist2), +inf for the
+ * sentinel.  vu_edt needs no workspace: the output holds the column pass.
+ *
+ * Surface statistics between the boundary sets P (of pred) and G (of gt), per
+ * plane.  d^2 P->G of a pixel of P is its squared distance to the nearest pixel
+ * of G, d^2 G->P likewise.  stats [planes][8] int64, overwritten:
+ *   0 n_P   1 n_G   2 max d^2 P->G   3 max d^2 G->P
+ *   4, 5 the q-th percentile of d^2 P->G, G->P: nearest rank in integers, the
+ *        value of rank (q n + 99) / 100, 1-based, ascending; q in 1..100
+ *   6, 7 the number of pixels of P, of G with d^2 <= tol2 (tol2 >= 0; for a
+ *        tolerance t in pixels the caller passes (int)(t t), formed in fp64)
+ * sums [planes][2] fp64 = the sum of sqrt((double)d^2) over P->G, over G->P.
+ * With n_P == 0 or n_G == 0 the plane is undefined: columns 2..7 are -1, both
+ * sums 0; the sentinel never enters a sum, a maximum or a count.  The sums are
+ * formed in a fixed order (no floating-point atomics): two runs are bitwise
+ * equal.  workspace: vu_edt_workspace_bytes(planes, H, W) bytes (-1 for sizes
+ * that are refused).
+ *
+ * vu_surface_metrics: out [planes][4] fp64 =
+ *   hd = sqrt(max(c2, c3)),  hd_q = max(sqrt c4, sqrt c5),
+ *   assd = (s0 + s1) / (n_P + n_G),  nsd = (c6 + c7) / (n_P + n_G),
+ * all four NaN on an undefined plane.  acc [4] fp64 and nacc [2] int64
+ * (optional, both or neither) are running accumulators: the four values of the
+ * defined planes are ADDED to acc in plane order, the number of defined planes
+ * to nacc[0] and planes to nacc[1]; the pooled metric is acc[k] / nacc[0], NaN
+ * when no plane is defined.
+ *
+ * hipErrorInvalidValue, nothing launched: a negative size, H or W above
+ * VU_EDT_MAX_DIM, an unknown dtype or mode, out_f32 not 0 or 1, q outside
+ * 1..100, tol2 < 0, one of acc and nacc without the other, then (no size zero)
+ * a null pointer.  A size of zero returns 0. */
+#define VU_EDT_TO_FOREGROUND 0
+#define VU_EDT_TO_BACKGROUND 1
+#define VU_EDT_TO_BOUNDARY 2
+#define VU_EDT_INF 2147483647
+#define VU_EDT_MAX_DIM 16384
+int64_t vu_edt_workspace_bytes(int64_t planes, int H, int W);
+int vu_edt(const void* x, int dtype, float threshold, int mode, int64_t planes,
+           int H, int W, void* out, int out_f32, void* stream);
+int vu_edt_boundary(const void* x, int dtype, float threshold, int64_t planes,
+                    int H, int W, uint8_t* out, void* stream);
+int vu_surface_stats(const void* pred, int dtype, float threshold,
+                     const void* gt, int gt_dtype, int64_t planes, int H,
+                     int W, int q, int tol2, int64_t* stats, double* sums,
+                     void* workspace, void* stream);
+int vu_surface_metrics(const int64_t* stats, const double* sums,
+                       int64_t planes, double* out, double* acc, int64_t* nacc,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

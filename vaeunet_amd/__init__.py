@@ -8,6 +8,8 @@ Calibration / uncertainty metrics (utils/uncertainty_metrics.py's numbers; unpin
   calibration.{calib_hist, calib_metrics, CalibrationMeter}
 Lesion-level evaluation (unpinned): lesions.{label_components, component_areas,
   remove_small_components, lesion_counts, lesion_metrics, LesionMeter}
+Boundary metrics (unpinned): surface.{distance_transform, boundary, surface_stats,
+  surface_metrics, SurfaceMeter}
 Patch loader with device-side training augmentation (unpinned):
   data.{PatchCache, TrainAugment, augment_patches}
 Dispatcher ops: torch.ops.vaeunet.* (vaeunet_amd.ops)
@@ -18,7 +20,8 @@ from .unet_resnet import UNetResNet, DecoderBlock  # noqa: F401,E402
 from . import ops  # noqa: F401,E402  (registers torch.ops.vaeunet.*)
 from .metrics import (dice_score, iou_score, precision_recall, specificity, accuracy,  # noqa: F401,E402
                       get_all_metrics, seg_counts, seg_metrics, SegmentationMeter)
-from .evaluate import evaluate, evaluate_with_lesions  # noqa: F401,E402
+from .evaluate import evaluate, evaluate_with_lesions, evaluate_with_surface  # noqa: F401,E402
 from .calibration import calib_hist, calib_metrics, CalibrationMeter, CalibCounts  # noqa: F401,E402
 from .lesions import (label_components, component_areas, remove_small_components, lesion_counts,  # noqa: F401,E402
                       lesion_metrics, LesionMeter)
+from .surface import (distance_transform, boundary, surface_stats, surface_metrics, SurfaceMeter)  # noqa: F401,E402

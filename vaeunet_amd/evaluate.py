@@ -59,10 +59,27 @@ def evaluate_with_lesions(net, dataloader, device, lesion_meter, amp=True, align
     return _evaluate(net, dataloader, device, amp, align_corners, max_batches, lesion_meter)
 
 
+def evaluate_with_surface(net, dataloader, device, surface_meter, lesion_meter=None, amp=True, align_corners=False,
+                          max_batches=None):
+    """``evaluate`` plus boundary metrics.  surface_meter: a
+    ``surface.SurfaceMeter`` (not reset here); lesion_meter: optionally a
+    ``lesions.LesionMeter`` as in ``evaluate_with_lesions``.  Each batch's hard
+    prediction at mask resolution -- written by the counts pass -- and its mask
+    go to the meter(s), and the result gains ``surface_hd``, ``surface_hd<q>``
+    (q = the meter's percentile: ``surface_hd95``), ``surface_assd``,
+    ``surface_nsd`` (floats: means over the planes where both boundaries exist,
+    NaN when there is none) and ``surface_n_defined`` (int), plus the lesion
+    keys with a lesion meter, all read in the same single transfer as the pixel
+    scores."""
+    if surface_meter is None:
+        raise ValueError("evaluate_with_surface: surface_meter is required (evaluate() is the loop without one)")
+    return _evaluate(net, dataloader, device, amp, align_corners, max_batches, lesion_meter, surface_meter)
+
+
 @torch.inference_mode()
-def _evaluate(net, dataloader, device, amp, align_corners, max_batches, lesion_meter):
-    """the loop of both; with lesion_meter None the launches, the result keys and the one synchronisation are those
-    of evaluate() before the lesion scores existed"""
+def _evaluate(net, dataloader, device, amp, align_corners, max_batches, lesion_meter, surface_meter=None):
+    """the loop of all three; with no meter the launches, the result keys and the one synchronisation are those of
+    evaluate() before the lesion scores existed"""
     device = torch.device(device)
     was_training = net.training
     net.eval()
@@ -81,18 +98,21 @@ def _evaluate(net, dataloader, device, amp, align_corners, max_batches, lesion_m
             with torch.autocast(device.type, dtype=torch.bfloat16, enabled=bool(amp)):
                 out = net(image)
             logits = out[0] if isinstance(out, (tuple, list)) else out
-            if lesion_meter is None:
+            if lesion_meter is None and surface_meter is None:
                 meter.update(logits, mask)
             else:
                 hard = torch.empty(mask.shape, dtype=torch.uint8, device=device)
                 meter.update(logits, mask, hard_mask=hard)
-                lesion_meter.update(hard, mask)
+                if lesion_meter is not None:
+                    lesion_meter.update(hard, mask)
+                if surface_meter is not None:
+                    surface_meter.update(hard, mask)
     finally:
         net.train(was_training)
     if meter.batches == 0:
         raise ValueError("evaluate: the dataloader produced no batch")
-    if lesion_meter is not None:
-        return _with_lesions(meter, lesion_meter)
+    if lesion_meter is not None or surface_meter is not None:
+        return _with_meters(meter, lesion_meter, surface_meter)
     # one transfer (and the only host synchronisation) for all twelve numbers
     both = torch.stack([meter.values("batch_mean"), meter.values("pooled")]).cpu()
     res = {k: both[0, i].item() for i, k in enumerate(METRIC_NAMES)}
@@ -101,18 +121,29 @@ def _evaluate(net, dataloader, device, amp, align_corners, max_batches, lesion_m
     return res
 
 
-def _with_lesions(meter, lesion_meter):
-    """the result dict with the lesion keys: all numbers in one fp64 transfer (fp32 values and counts below 2^53
-    pass through fp64 unchanged)"""
+def _with_meters(meter, lesion_meter, surface_meter):
+    """the result dict with the lesion and / or surface keys: all numbers in one fp64 transfer (fp32 values and counts
+    below 2^53 pass through fp64 unchanged)"""
     k = len(METRIC_NAMES)
-    totals = lesion_meter.counts().sum(0)
-    flat = torch.cat([meter.values("batch_mean").double(), meter.values("pooled").double(),
-                      lesion_meter.values().double(), totals.double()]).cpu()
+    parts = [meter.values("batch_mean").double(), meter.values("pooled").double()]
+    if lesion_meter is not None:
+        parts += [lesion_meter.values().double(), lesion_meter.counts().sum(0).double()]
+    if surface_meter is not None:
+        parts += [surface_meter.values(), surface_meter.counts().double()]
+    flat = torch.cat(parts).cpu()
     res = {name: flat[i].item() for i, name in enumerate(METRIC_NAMES)}
     res.update({f"pooled_{name}": flat[k + i].item() for i, name in enumerate(METRIC_NAMES)})
     res["batches"] = meter.batches
-    for i, name in enumerate(LESION_METRIC_NAMES):
-        res[f"lesion_{name}"] = flat[2 * k + i].item()
-    res["lesion_n_gt"] = int(flat[2 * k + 3].item())
-    res["lesion_n_pred"] = int(flat[2 * k + 5].item())
+    at = 2 * k
+    if lesion_meter is not None:
+        for i, name in enumerate(LESION_METRIC_NAMES):
+            res[f"lesion_{name}"] = flat[at + i].item()
+        res["lesion_n_gt"] = int(flat[at + 3].item())
+        res["lesion_n_pred"] = int(flat[at + 5].item())
+        at += 7
+    if surface_meter is not None:
+        names = ("hd", f"hd{surface_meter.percentile}", "assd", "nsd")
+        for i, name in enumerate(names):
+            res[f"surface_{name}"] = flat[at + i].item()
+        res["surface_n_defined"] = int(flat[at + 4].item())
     return res

@@ -40,6 +40,9 @@ Reference ops each one replaces:
                                  bitwise a selection of the inputs)
   label_components /             connected-component labels per (image, class) plane and the removal of small
   remove_small_components        components (DESIGN.md §4.11's definitions; canonical labels = 1 + first raster pixel)
+  distance_transform             scipy.ndimage.distance_transform_edt per (image, class) plane, exact and squared
+                                 (DESIGN.md §4.12's definitions; int32 d^2, or fp32 sqrt; sites = background,
+                                 foreground or the 4-neighbour boundary)
 """
 import ctypes as C
 import types
@@ -53,6 +56,7 @@ from . import calibration as _calibration
 from . import data as _data
 from . import lesions as _lesions
 from . import metrics as _metrics
+from . import surface as _surface
 from ._lib import call, ptr, query, stream
 from .engine import conv_layout, convT_layout, w3x3_dgrad, w3x3_fwd, wT_dgrad, wT_fwd
 from .loss import _check_focal_cfg, _dense_pair, _focal_bwd, _focal_fwd, _focal_pair
@@ -884,8 +888,29 @@ def _(x, min_area, connectivity=8, threshold=None):
     return torch.empty(x.shape, dtype=torch.uint8, device=x.device)
 
 
+# ---- distance transform ---------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::distance_transform", mutates_args=(), device_types="cuda")
+def distance_transform(x: torch.Tensor, mode: str = "background", threshold: Optional[float] = None,
+                       squared: bool = True) -> torch.Tensor:
+    """vaeunet_amd.surface.distance_transform: x [B, C, H, W] uint8 / bool (nonzero
+    is foreground) or float32 (x > threshold) -> the exact squared Euclidean
+    distance of every pixel to the nearest site of its plane, int32 (2^31 - 1 on a
+    plane without a site), or float32 sqrt with squared=False (+inf there); mode
+    names the sites: "background", "foreground" or "boundary" (DESIGN.md §4.12).
+    Not differentiable."""
+    return _surface.distance_transform(x, mode, threshold, squared)
+
+
+@distance_transform.register_fake
+def _(x, mode="background", threshold=None, squared=True):
+    if mode not in _surface.MODES:
+        raise ValueError(f"vaeunet::distance_transform: mode must be one of {', '.join(_surface.MODES)}, got {mode!r}")
+    _surface._check_x(x, threshold, "vaeunet::distance_transform")
+    return torch.empty(x.shape, dtype=torch.int32 if squared else torch.float32, device=x.device)
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
        "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch", "clahe", "blur_separable",
-       "median_blur", "label_components", "remove_small_components")
+       "median_blur", "label_components", "remove_small_components", "distance_transform")
