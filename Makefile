@@ -18,6 +18,8 @@ build/median.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 build/ccl.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 # the distance transform's passes must not use scratch
 build/edt.o: FLAGS += -Rpass-analysis=kernel-resource-usage
+# the signed distance map's passes must not use scratch either
+build/sdf.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 
 $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJ) -o $@

@@ -1338,6 +1338,59 @@ int vu_surface_metrics(const int64_t* stats, const double* sums,
                        int64_t planes, double* out, double* acc, int64_t* nacc,
                        void* stream);
 
+/* ---- boundary loss: signed distance map and the fused loss ---------------- */
+/* DESIGN.md 4.13; this project's own definitions, stated so that they equal
+ * the one_hot2dist / boundary loss of Kervadec et al.
+ *
+ * Planes, foreground, dtypes and thresholds are those of the boundary metrics
+ * above (VU_CCL_U8: nonzero; VU_CCL_F32: p > threshold, strictly; NaN is
+ * background).
+ *
+ * Signed squared distance: int32 s2[y][x], exact:
+ *   + d^2 to the nearest foreground pixel, at a background pixel
+ *   - d^2 to the nearest background pixel, at a foreground pixel
+ *   0 everywhere on a plane with no foreground or no background (no boundary,
+ *     no pull)
+ * On a plane that has both classes s2 is never 0.  No sentinel appears in the
+ * output.
+ *
+ * Signed distance map: float32 phi, the value rounded once from fp64:
+ *   s2 > 0:  phi = (float)sqrt((double)s2)
+ *   s2 < 0:  phi = (float)(1.0 - sqrt((double)(-s2)))   0 on the foreground
+ *                                                        pixels at the boundary
+ *   s2 == 0: phi = 0
+ * then clamped to [-clip, clip]; clip > 0, +inf for none.
+ *
+ * vu_sdf writes s2 (out_f32 = 0; clip must still be > 0 and is not used) or
+ * phi (out_f32 = 1) of every plane of x [planes][H][W] into out, which also
+ * holds the column pass: no workspace.  H <= VU_EDT_MAX_DIM and W <=
+ * VU_SDF_MAX_W = 8192: the row pass keeps both 16-bit rows of vertical
+ * distances in LDS, 4 W bytes <= 32 KB.
+ *
+ * Boundary loss over n elements, p = sigmoid(logits):
+ *   loss = (1 / n) sum phi p        d loss / d logits = g phi p (1 - p) / n
+ * An element with a NaN logit or a non-finite phi adds nothing and gets
+ * gradient 0; it still counts in n.  sums [3] fp64 = sum phi p, sum |phi| p,
+ * the number of skipped elements (block partials in fp64, a fixed summation
+ * order); loss[0] = (float)(sums[0] / n) (optional).  gscale: a device scalar
+ * g, NULL = 1.  No float atomics; the grid is a function of n and the pointers'
+ * alignment only, so two runs are bitwise equal.  workspace:
+ * vu_boundary_loss_workspace_bytes.
+ *
+ * hipErrorInvalidValue, nothing launched: vu_sdf on a negative size, H above
+ * VU_EDT_MAX_DIM, W above VU_SDF_MAX_W, an unknown dtype, out_f32 not 0 or 1,
+ * clip not > 0, then (no size zero) a null pointer; a size of zero returns 0.
+ * vu_boundary_loss_* on n < 1 or a null pointer other than loss / gscale. */
+#define VU_SDF_MAX_W 8192
+int vu_sdf(const void* x, int dtype, float threshold, int64_t planes, int H,
+           int W, void* out, int out_f32, float clip, void* stream);
+int64_t vu_boundary_loss_workspace_bytes(void);
+int vu_boundary_loss_fwd(const float* logits, const float* phi, int64_t n,
+                         double* sums, float* loss, double* workspace,
+                         void* stream);
+int vu_boundary_loss_bwd(const float* logits, const float* phi, int64_t n,
+                         const float* gscale, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

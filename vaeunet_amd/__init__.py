@@ -10,6 +10,8 @@ Lesion-level evaluation (unpinned): lesions.{label_components,
   remove_small_components, lesion_counts, lesion_metrics, LesionMeter}
 Boundary metrics (unpinned): surface.{distance_transform, boundary, surface_stats,
   surface_metrics, SurfaceMeter}
+Boundary loss (Kervadec et al.'s definitions): surface.signed_distance,
+  loss.{boundary_loss, BoundaryLoss, BoundaryAugmentedLoss}
 Patch loader with device-side training augmentation (unpinned):
   data.{PatchCache, TrainAugment, augment_patches}
 Dispatcher ops: torch.ops.vaeunet.* (vaeunet_amd.ops)
@@ -24,4 +26,6 @@ from .evaluate import evaluate, evaluate_with_lesions, evaluate_with_surface  # 
 from .calibration import calib_hist, calib_metrics, CalibrationMeter, CalibCounts  # noqa: F401,E402
 from .lesions import (label_components, component_areas, remove_small_components, lesion_counts,  # noqa: F401,E402
                       lesion_metrics, LesionMeter)
-from .surface import (distance_transform, boundary, surface_stats, surface_metrics, SurfaceMeter)  # noqa: F401,E402
+from .surface import (distance_transform, boundary, surface_stats, surface_metrics, SurfaceMeter,  # noqa: F401,E402
+                      signed_distance)
+from .loss import boundary_loss, BoundaryLoss, BoundaryAugmentedLoss  # noqa: F401,E402

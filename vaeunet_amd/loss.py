@@ -13,6 +13,11 @@ objective) run on the fused focal + Dice kernels of csrc/focal.hip; their
 definitions are written out in DESIGN.md §4.7 and are unpinned against the
 reference, so every constant is a constructor argument.
 
+boundary_loss / BoundaryLoss / BoundaryAugmentedLoss: the
+boundary loss of Kervadec et al., mean(phi * sigmoid(x)) with phi the signed
+distance map of the ground truth, computed on the device by csrc/sdf.hip and
+reduced by csrc/boundary_loss.hip; not part of the reference.
+
 Deviation, documented: the reference's ``.view(-1)`` (loss.py:17-18) raises on
 channels_last logits with more than one class; here the sums are taken in
 memory order, which equals the reference's result whenever it runs.
@@ -21,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import surface as _surface
 from ._lib import ptr, call, query, stream
 
 CL = torch.channels_last
@@ -224,6 +230,168 @@ class MASegmentationLoss(nn.Module):
                                   self.dice_weight, "mean")
         self.last_parts = parts
         return loss
+
+
+# ---- boundary loss --------------------------------------------
+def _boundary_inputs(inputs, what):
+    if not isinstance(inputs, torch.Tensor) or inputs.dim() not in (3, 4):
+        raise ValueError(f"{what}: inputs must be a [B, C, H, W] or [B, H, W] tensor, got "
+                         f"{tuple(inputs.shape) if isinstance(inputs, torch.Tensor) else type(inputs).__name__}")
+    if inputs.numel() == 0:
+        raise ValueError(f"{what}: empty input {tuple(inputs.shape)}")
+    return tuple(inputs.shape) if inputs.dim() == 4 else (inputs.shape[0], 1) + tuple(inputs.shape[1:])
+
+
+def _boundary_check(inputs, targets, phi, clip, threshold, what="boundary_loss"):
+    """Every ValueError, before a device is touched -> (shape [B, C, H, W], clip as a float, threshold)"""
+    shape = _boundary_inputs(inputs, what)
+    if (targets is None) == (phi is None):
+        raise ValueError(f"{what}: exactly one of targets and phi must be given")
+    c = _surface._check_clip(clip, what)
+    if phi is not None:
+        if clip is not None or threshold is not None:
+            raise ValueError(f"{what}: clip and threshold describe how phi is computed from targets; with phi= "
+                             "they must be None")
+        if not isinstance(phi, torch.Tensor) or phi.dtype != torch.float32 or tuple(phi.shape) != tuple(inputs.shape):
+            raise ValueError(f"{what}: phi must be a float32 tensor of the inputs' shape {tuple(inputs.shape)}")
+        return shape, c, None
+    if not isinstance(targets, torch.Tensor) or tuple(targets.shape) != tuple(inputs.shape):
+        raise ValueError(f"{what}: target shape {tuple(targets.shape) if isinstance(targets, torch.Tensor) else None} "
+                         f"!= input shape {tuple(inputs.shape)}")
+    if targets.dtype in (torch.uint8, torch.bool):
+        thr = 0.0
+    else:
+        thr = 0.5 if threshold is None else float(threshold)
+        if thr != thr:
+            raise ValueError(f"{what}: the threshold is NaN")
+    if shape[2] > _surface.VU_EDT_MAX_DIM or shape[3] > _surface.VU_SDF_MAX_W:
+        raise ValueError(f"{what}: planes of {shape[2]} x {shape[3]} pixels exceed the signed distance map's "
+                         f"H <= {_surface.VU_EDT_MAX_DIM}, W <= {_surface.VU_SDF_MAX_W}")
+    return shape, c, thr
+
+
+def _boundary_pair(inputs, phi):
+    """_dense_pair for (logits, phi): the shapes compared first, empty tensors refused"""
+    if tuple(phi.shape) != tuple(inputs.shape):
+        raise ValueError(f"phi shape {tuple(phi.shape)} != input shape {tuple(inputs.shape)}")
+    if inputs.numel() == 0:
+        raise ValueError("boundary_loss: empty input")
+    return _dense_pair(inputs, phi)
+
+
+def _boundary_fwd(x, phi):
+    """The two forward launches: (loss, sums fp64 [3] = sum phi p, sum |phi| p, skipped elements)."""
+    sums = torch.empty(3, dtype=torch.float64, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    ws = torch.empty(query("vu_boundary_loss_workspace_bytes") // 8, dtype=torch.float64, device=x.device)
+    call("vu_boundary_loss_fwd", ptr(x), ptr(phi), x.numel(), ptr(sums), ptr(loss), ptr(ws), stream())
+    return loss, sums
+
+
+def _boundary_bwd(x, phi, gout):
+    g = gout.float().contiguous()
+    grad = torch.empty_like(x)
+    call("vu_boundary_loss_bwd", ptr(x), ptr(phi), x.numel(), ptr(g), ptr(grad), stream())
+    return grad
+
+
+class _Boundary(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, phi):
+        loss, sums = _boundary_fwd(x, phi)
+        ctx.save_for_backward(x, phi)
+        ctx.mark_non_differentiable(sums)
+        ctx.set_materialize_grads(False)
+        return loss, sums
+
+    @staticmethod
+    def backward(ctx, gout, _gsums):
+        if gout is None:
+            return None, None
+        x, phi = ctx.saved_tensors
+        return _boundary_bwd(x, phi, gout), None
+
+
+def _boundary(inputs, targets, phi, clip, threshold):
+    shape, c, thr = _boundary_check(inputs, targets, phi, clip, threshold)
+    if inputs.device.type != "cuda":
+        raise RuntimeError("vaeunet_amd losses run on MI355X (HIP) devices only")
+    as4 = (lambda a: a) if inputs.dim() == 4 else (lambda a: a.unsqueeze(1))
+    x4 = as4(inputs)
+    if phi is None:
+        with torch.no_grad():
+            t = as4(targets.to(x4.device))
+            if t.dtype not in (torch.uint8, torch.bool, torch.float32):
+                t = t.float()
+            phi4 = _surface._launch_sdf(_surface._dense(t), thr, False, c)
+    else:
+        phi4 = as4(phi.detach())
+    x, f = _dense_pair(x4, phi4)
+    return _Boundary.apply(x, f)
+
+
+def boundary_loss(inputs, targets=None, *, phi=None, clip=None, threshold=None):
+    """The boundary loss of Kervadec et al.: the mean over all
+    elements of phi * sigmoid(inputs), phi the signed distance map of the
+    ground truth (``surface.signed_distance``: positive outside the mask,
+    <= 0 inside).  inputs [B, C, H, W], or [B, H, W] viewed as C = 1, any memory
+    format.  Exactly one of ``targets`` (a mask of the inputs' shape: uint8 /
+    bool nonzero, anything else ``> threshold``, 0.5 by default; phi is
+    computed from it on the device, under ``no_grad``, clamped to [-clip, clip]
+    when ``clip`` is given) and ``phi`` (a precomputed float32 map) is given.
+    The gradient goes to ``inputs`` only.  An element with a NaN logit or a
+    non-finite phi adds nothing and gets gradient 0.  No host synchronisation."""
+    return _boundary(inputs, targets, phi, clip, threshold)[0]
+
+
+class BoundaryLoss(nn.Module):
+    """``boundary_loss(inputs, targets, clip=clip)`` as a module."""
+
+    def __init__(self, clip=None):
+        super().__init__()
+        _surface._check_clip(clip, "BoundaryLoss")
+        self.clip = clip
+
+    def forward(self, inputs, targets):
+        return boundary_loss(inputs, targets, clip=self.clip)
+
+
+class BoundaryAugmentedLoss(nn.Module):
+    """``base(inputs, targets) + weight * boundary_loss(inputs, targets, clip=clip)``.
+
+    ``weight`` is a scalar buffer that lives on the device of the first batch;
+    ``set_weight(v)`` fills it in place, so a schedule that raises the weight
+    from epoch to epoch works under graph replay without recapture.  After a
+    call, ``self.last_parts`` holds the device tensor [base, boundary]."""
+
+    def __init__(self, base, weight=0.01, clip=None):
+        super().__init__()
+        if not callable(base):
+            raise ValueError(f"BoundaryAugmentedLoss: base must be a loss module or function, got {type(base).__name__}")
+        _surface._check_clip(clip, "BoundaryAugmentedLoss")
+        self.base = base
+        self.clip = clip
+        self.register_buffer("weight", torch.tensor(self._check_weight(weight), dtype=torch.float32))
+        self.last_parts = None
+
+    @staticmethod
+    def _check_weight(v):
+        v = float(v)
+        if v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"BoundaryAugmentedLoss: weight must be finite, got {v}")
+        return v
+
+    def set_weight(self, v):
+        self.weight.fill_(self._check_weight(v))
+
+    def forward(self, inputs, targets):
+        _boundary_check(inputs, targets, None, self.clip, None, "BoundaryAugmentedLoss")
+        if self.weight.device != inputs.device:
+            self.weight = self.weight.to(inputs.device)
+        base = self.base(inputs, targets)
+        bnd = boundary_loss(inputs, targets, clip=self.clip)
+        self.last_parts = torch.stack([base.detach().float(), bnd.detach()])
+        return base + self.weight * bnd
 
 
 class KLAnnealer:

@@ -43,6 +43,9 @@ Reference ops each one replaces:
   distance_transform             scipy.ndimage.distance_transform_edt per (image, class) plane, exact and squared
                                  (DESIGN.md §4.12's definitions; int32 d^2, or fp32 sqrt; sites = background,
                                  foreground or the 4-neighbour boundary)
+  signed_distance                Kervadec et al.'s one_hot2dist per (image, class) plane: scipy's transform of the
+                                 mask and of its complement, signed, in one signed transform
+  boundary_loss                  their boundary (surface) loss: mean(phi * sigmoid(logits))
 """
 import ctypes as C
 import types
@@ -59,7 +62,8 @@ from . import metrics as _metrics
 from . import surface as _surface
 from ._lib import call, ptr, query, stream
 from .engine import conv_layout, convT_layout, w3x3_dgrad, w3x3_fwd, wT_dgrad, wT_fwd
-from .loss import _check_focal_cfg, _dense_pair, _focal_bwd, _focal_fwd, _focal_pair
+from .loss import (_boundary_bwd, _boundary_fwd, _boundary_pair, _check_focal_cfg, _dense_pair, _focal_bwd, _focal_fwd,
+                   _focal_pair)
 
 _NS = "vaeunet"
 
@@ -909,8 +913,67 @@ def _(x, mode="background", threshold=None, squared=True):
     return torch.empty(x.shape, dtype=torch.int32 if squared else torch.float32, device=x.device)
 
 
+# ---- signed distance map and boundary loss ------------------------------------------------------------
+def _sdf_check(x, threshold, squared, clip):
+    what = "vaeunet::signed_distance"
+    c = _surface._check_clip(clip, what)
+    if squared and clip is not None:
+        raise ValueError(f"{what}: clip applies to the float32 map, not to squared=True")
+    return _surface._check_sdf_input(x, threshold, what), c
+
+
+@torch.library.custom_op(f"{_NS}::signed_distance", mutates_args=(), device_types="cuda")
+def signed_distance(x: torch.Tensor, threshold: Optional[float] = None, squared: bool = False,
+                    clip: Optional[float] = None) -> torch.Tensor:
+    """vaeunet_amd.surface.signed_distance: x [B, C, H, W] uint8 / bool (nonzero is
+    foreground) or float32 (x > threshold) -> float32 phi = sqrt(s2) outside the
+    mask, 1 - sqrt(-s2) inside, clamped to [-clip, clip]; or, with squared=True,
+    int32 s2 = +d^2 to the nearest foreground pixel outside, -d^2 to the nearest
+    background pixel inside; 0 on a plane with one class only.
+    Not differentiable."""
+    return _surface.signed_distance(x, threshold, squared, clip)
+
+
+@signed_distance.register_fake
+def _(x, threshold=None, squared=False, clip=None):
+    _sdf_check(x, threshold, squared, clip)
+    return torch.empty(x.shape, dtype=torch.int32 if squared else torch.float32, device=x.device)
+
+
+@torch.library.custom_op(f"{_NS}::boundary_loss", mutates_args=(), device_types="cuda")
+def boundary_loss(logits: torch.Tensor, phi: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """mean(phi * sigmoid(logits)) in one fused reduction
+    (vaeunet_amd.loss.boundary_loss(logits, phi=phi); fp64 block sums, loss formed
+    on the device, no host sync).  Returns (loss, sums): sums = the fp64 {sum phi p,
+    sum |phi| p, skipped elements}.  The gradient goes to logits only."""
+    x, f = _boundary_pair(logits, phi)
+    return _boundary_fwd(x, f)
+
+
+@boundary_loss.register_fake
+def _(logits, phi):
+    if tuple(phi.shape) != tuple(logits.shape):
+        raise ValueError(f"phi shape {tuple(phi.shape)} != input shape {tuple(logits.shape)}")
+    return (torch.empty((), dtype=torch.float32, device=logits.device),
+            torch.empty(3, dtype=torch.float64, device=logits.device))
+
+
+def _boundary_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+
+
+def _boundary_backward(ctx, g, _gsums):
+    logits, phi = ctx.saved_tensors
+    x, f = _dense_pair(logits, phi)
+    return _boundary_bwd(x, f, g).to(logits.dtype), None
+
+
+boundary_loss.register_autograd(_boundary_backward, setup_context=_boundary_setup)
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
        "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch", "clahe", "blur_separable",
-       "median_blur", "label_components", "remove_small_components", "distance_transform")
+       "median_blur", "label_components", "remove_small_components", "distance_transform", "signed_distance",
+       "boundary_loss")

@@ -13,14 +13,18 @@ strictly (NaN is background); ground-truth masks are foreground when nonzero
 first).  A boundary pixel is a foreground pixel with at least one of its four
 neighbours background or outside the plane.  Distances are in pixels.
 
-Nothing in ``surface_stats`` or ``SurfaceMeter.update`` synchronises the host.
+``signed_distance`` (csrc/sdf.hip) is the signed distance map
+the boundary loss of ``vaeunet_amd.loss`` multiplies the probabilities with.
+
+Nothing in ``surface_stats``, ``SurfaceMeter.update`` or ``signed_distance``
+synchronises the host.
 """
 import numbers
 
 import torch
 
-from ._lib import (VU_EDT_INF, VU_EDT_MAX_DIM, VU_EDT_TO_BACKGROUND, VU_EDT_TO_BOUNDARY, VU_EDT_TO_FOREGROUND, call,
-                   ptr, query, stream)
+from ._lib import (VU_EDT_INF, VU_EDT_MAX_DIM, VU_EDT_TO_BACKGROUND, VU_EDT_TO_BOUNDARY, VU_EDT_TO_FOREGROUND,
+                   VU_SDF_MAX_W, call, ptr, query, stream)
 from .lesions import _CODES, _check_input, _check_planes, _dense
 
 MODES = {"foreground": VU_EDT_TO_FOREGROUND, "background": VU_EDT_TO_BACKGROUND, "boundary": VU_EDT_TO_BOUNDARY}
@@ -109,6 +113,48 @@ def boundary(x, threshold=None):
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     call("vu_edt_boundary", ptr(x), _CODES[x.dtype], thr, B * Cn, H, W, ptr(out), stream())
     return out
+
+
+def _check_clip(clip, what):
+    """-> the clip as a float, +inf for None"""
+    if clip is None:
+        return float("inf")
+    if isinstance(clip, bool) or not isinstance(clip, numbers.Real) or not float(clip) > 0.0:   # NaN fails
+        raise ValueError(f"{what}: clip must be a number > 0 or None, got {clip!r}")
+    return float(clip)
+
+
+def _check_sdf_input(x, threshold, what, name="x"):
+    thr = _check_x(x, threshold, what, name)
+    if x.shape[3] > VU_SDF_MAX_W:
+        raise ValueError(f"{what}: {name} of width {x.shape[3]} exceeds the signed distance map's W <= {VU_SDF_MAX_W}")
+    return thr
+
+
+def _launch_sdf(x, thr, squared, clip):
+    """x dense and validated, on the device; clip a float > 0"""
+    B, Cn, H, W = x.shape
+    out = torch.empty(x.shape, dtype=torch.int32 if squared else torch.float32, device=x.device)
+    call("vu_sdf", ptr(x), _CODES[x.dtype], thr, B * Cn, H, W, ptr(out), 0 if squared else 1, clip, stream())
+    return out
+
+
+def signed_distance(x, threshold=None, squared=False, clip=None):
+    """The signed distance map of every plane of ``x`` [B, C, H, W] (uint8, bool
+    or float32), DESIGN.md §4.13: ``squared=True`` returns int32 ``s2``, +d^2
+    to the nearest foreground pixel at a background pixel, -d^2 to the nearest
+    background pixel at a foreground pixel; ``squared=False`` returns float32
+    ``phi`` = sqrt(s2) outside, 1 - sqrt(-s2) inside (0 on the foreground
+    pixels at the boundary), clamped to [-clip, clip] when ``clip`` is given.
+    A plane without foreground or without background is 0 everywhere.  One
+    signed transform: two launches, no host synchronisation.  W <= 8192."""
+    what = "signed_distance"
+    c = _check_clip(clip, what)
+    if squared and clip is not None:
+        raise ValueError(f"{what}: clip applies to the float32 map, not to squared=True")
+    thr = _check_sdf_input(x, threshold, what)
+    _need_device(x, what)
+    return _launch_sdf(_dense(x), thr, bool(squared), c)
 
 
 def _stats(pred, masks, thr, q, tol2, stats, sums, buf):
