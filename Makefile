@@ -20,6 +20,8 @@ build/ccl.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 build/edt.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 # the signed distance map's passes must not use scratch either
 build/sdf.o: FLAGS += -Rpass-analysis=kernel-resource-usage
+# the sample Gram kernel must not use scratch
+build/sampleset.o: FLAGS += -Rpass-analysis=kernel-resource-usage
 
 $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJ) -o $@

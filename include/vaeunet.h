@@ -1391,6 +1391,72 @@ int vu_boundary_loss_fwd(const float* logits, const float* phi, int64_t n,
 int vu_boundary_loss_bwd(const float* logits, const float* phi, int64_t n,
                          const float* gscale, float* grad, void* stream);
 
+/* ---- sample-set metrics: pairwise overlap matrix, GED, diversity ---------- */
+/* DESIGN.md 4.14; this project's own definitions, unpinned against any
+ * reference code.
+ *
+ * Planes and foreground are those of the lesion-level evaluation above.  A
+ * plane is one (image, class) slice of H W pixels; planes never interact.
+ * samples is a contiguous [S][planes][H W] tensor, truths a contiguous
+ * [M][planes][H W] tensor with a dtype code of its own.  A sample element is
+ * foreground when nonzero (VU_CCL_U8; threshold is not used) or when
+ * p > threshold, strictly (VU_CCL_F32; a NaN is background); a truth element
+ * when nonzero or when > 0.5, strictly.  S >= 1, M >= 0 (truths may then be
+ * null, truth_dtype is not read), K = S + M <= VU_SAMPLESET_MAX.
+ *
+ * vu_sample_gram: gram [planes][K][K] int64.  Columns 0 .. S - 1 are the
+ * samples in order, columns S .. K - 1 the truths.  gram[p][i][j] = the number
+ * of pixels of plane p that are foreground in column i and in column j: the
+ * matrix is full and symmetric, both triangles and the diagonal are written,
+ * and the diagonal holds each column's area.  accumulate = 0 overwrites gram
+ * (a zeroing memset on the stream, then the kernel), accumulate = 1 ADDS to it.
+ * Every input element is read once, nothing but gram is written, the
+ * arithmetic is integer and the only atomics are 64-bit integer adds into
+ * gram: the result does not depend on the launch geometry and two runs are
+ * bitwise equal.  A block sweeps VU_SAMPLESET_STEP pixels of a plane per step
+ * when H W is a multiple of VU_SAMPLESET_VEC and both base pointers are
+ * 16-byte (VU_CCL_U8: 4-byte) aligned, VU_SAMPLESET_STEP / VU_SAMPLESET_VEC
+ * pixels otherwise; a plane gets one block per VU_SAMPLESET_MIN_STEPS steps,
+ * and the grid is capped at VU_SAMPLESET_GRID blocks, which then walk further.
+ *
+ * vu_sampleset_metrics: out [planes][VU_SAMPLESET_NMETRICS] fp64 from gram, S
+ * and M, overwritten.  For columns a, b with I = G[a][b], |a| = G[a][a],
+ * U = |a| + |b| - I:
+ *   d(a, b)    = 1 - I / U,          0 when U = 0
+ *   Dice(a, b) = 2 I / (|a| + |b|),  1 when both are empty
+ * Every quotient is fp64 from the integers; every sum is fp64, from 0, in
+ * row-major order (i outer, j inner), so every value is a deterministic
+ * function of the integers.  Output columns:
+ *   0 ged2             2 cross - diversity - truth_diversity
+ *   1 cross            mean of d(s_i, y_m) over the S M pairs
+ *   2 diversity        mean of d(s_i, s_j) over all S S ordered pairs, the
+ *                      diagonal included (Kohl et al.'s convention)
+ *   3 truth_diversity  the same over the M M truth pairs (0 when M = 1)
+ *   4 dice_mean        mean of Dice(s_i, y_m) over the S M pairs
+ *   5 dice_min         their minimum
+ *   6 dice_max         their maximum
+ *   7 area_mean        mean of |s_i| over the samples
+ *   8 area_std         population standard deviation of |s_i|: the square root
+ *                      of the mean of (|s_i| - area_mean)^2
+ * With M = 0 columns 0, 1, 3, 4, 5 and 6 are NaN; 2, 7 and 8 are defined.
+ *
+ * hipErrorInvalidValue, nothing launched: a negative size, S < 1, M < 0,
+ * K > VU_SAMPLESET_MAX, an unknown dtype (truth_dtype only when M > 0),
+ * accumulate not 0 or 1, H W above VU_CCL_MAX_PLANE, then (no size zero) a
+ * null pointer.  A size of zero (planes, H or W) returns 0. */
+#define VU_SAMPLESET_MAX 64
+#define VU_SAMPLESET_NMETRICS 9
+#define VU_SAMPLESET_GRID 2048
+#define VU_SAMPLESET_STEP 1024
+#define VU_SAMPLESET_VEC 4
+#define VU_SAMPLESET_MIN_STEPS 4
+int vu_sample_gram(const void* samples, int dtype, float threshold,
+                   const void* truths, int truth_dtype, int S, int M,
+                   int64_t planes, int H, int W, int64_t* gram, int accumulate,
+                   void* stream);
+int vu_sampleset_metrics(const int64_t* gram, int S, int M, int64_t planes,
+                         double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

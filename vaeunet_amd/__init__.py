@@ -12,6 +12,8 @@ Boundary metrics (unpinned): surface.{distance_transform, boun
   surface_metrics, SurfaceMeter}
 Boundary loss (Kervadec et al.'s definitions): surface.signed_distance,
   loss.{boundary_loss, BoundaryLoss, BoundaryAugmentedLoss}
+Sample-set metrics (unpinned): samples.{sample_gram, sample_set_metrics, SampleSetMeter,
+  SAMPLESET_METRIC_NAMES}, inference.sample_set_scores
 Patch loader with device-side training augmentation (unpinned):
   data.{PatchCache, TrainAugment, augment_patches}
 Dispatcher ops: torch.ops.vaeunet.* (vaeunet_amd.ops)
@@ -29,3 +31,4 @@ from .lesions import (label_components, component_areas, remove_small_components
 from .surface import (distance_transform, boundary, surface_stats, surface_metrics, SurfaceMeter,  # noqa: F401,E402
                       signed_distance)
 from .loss import boundary_loss, BoundaryLoss, BoundaryAugmentedLoss  # noqa: F401,E402
+from .samples import sample_gram, sample_set_metrics, SampleSetMeter, SAMPLESET_METRIC_NAMES  # noqa: F401,E402

@@ -12,6 +12,9 @@ results:
   ``get_segmentation_distribution_from_image`` (578-652) on an image tensor
   (the dataset lookup is out of scope).
 
+``sample_set_scores`` has no counterpart in the reference: it scores the samples
+of ``segmentation_distribution`` as a set against a mask.
+
 What differs from the reference is HOW it runs:
 
 * the encoder runs ONCE per image (per patch batch), and the N latent samples
@@ -38,6 +41,7 @@ from . import engine as E
 from . import kernels as K
 from . import vae_engine as V
 from ._lib import F32
+from .samples import sample_gram, sample_set_metrics
 
 CL = torch.channels_last
 
@@ -345,6 +349,20 @@ def segmentation_distribution(model, img, num_samples=32, patch_size=None, overl
         else:
             segs[s0:s0 + n] = predict_full_image(model, img, z4).view(n, 1, H, W)
     return segs, mu, logvar
+
+
+@torch.no_grad()
+def sample_set_scores(model, img, mask, num_samples=32, threshold=0.5, **kw):
+    """``segmentation_distribution(model, img, num_samples, **kw)`` scored as a set
+    against ``mask`` ([1, 1, H, W], or [M, 1, 1, H, W] for M annotations): returns
+    (scores, mu, logvar), scores = the fp64 [1, 1, 9] row of
+    ``samples.sample_set_metrics`` (columns ``SAMPLESET_METRIC_NAMES``: GED^2,
+    diversity, Dice spread, area variability) of the samples thresholded at
+    ``threshold``.  The samples never leave the device and no thresholded copy
+    is made."""
+    segs, mu, logvar = segmentation_distribution(model, img, num_samples, **kw)
+    gram = sample_gram(segs, mask, threshold)
+    return sample_set_metrics(gram, segs.shape[0]), mu, logvar
 
 
 @torch.no_grad()

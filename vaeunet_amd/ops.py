@@ -46,6 +46,9 @@ Reference ops each one replaces:
   signed_distance                Kervadec et al.'s one_hot2dist per (image, class) plane: scipy's transform of the
                                  mask and of its complement, signed, in one signed transform
   boundary_loss                  their boundary (surface) loss: mean(phi * sigmoid(logits))
+  sample_gram                    the pairwise overlap counts between S thresholded samples and the ground truths
+                                 per (image, class) plane, the one object GED^2, sample diversity and the Dice
+                                 spread are functions of (DESIGN.md §4.14's definitions; int64, exact)
 """
 import ctypes as C
 import types
@@ -59,6 +62,7 @@ from . import calibration as _calibration
 from . import data as _data
 from . import lesions as _lesions
 from . import metrics as _metrics
+from . import samples as _samples
 from . import surface as _surface
 from ._lib import call, ptr, query, stream
 from .engine import conv_layout, convT_layout, w3x3_dgrad, w3x3_fwd, wT_dgrad, wT_fwd
@@ -971,9 +975,31 @@ def _boundary_backward(ctx, g, _gsums):
 boundary_loss.register_autograd(_boundary_backward, setup_context=_boundary_setup)
 
 
+# ---- sample-set metrics ------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::sample_gram", mutates_args=(), device_types="cuda")
+def sample_gram(samples: torch.Tensor, truths: Optional[torch.Tensor] = None,
+                threshold: Optional[float] = 0.5) -> torch.Tensor:
+    """vaeunet_amd.samples.sample_gram: samples [S, B, C, H, W] (or [S, C, H, W])
+    float32 (p > threshold) or uint8 / bool (nonzero), truths None, [B, C, H, W] or
+    [M, B, C, H, W] -> int64 [B, C, K, K], K = S + M <= 64: the number of pixels of
+    each plane that are foreground in column i and in column j.
+    Not differentiable."""
+    return _samples.sample_gram(samples, truths, threshold)
+
+
+@sample_gram.register_fake
+def _(samples, truths=None, threshold=0.5):
+    what = "vaeunet::sample_gram"
+    shape, _thr = _samples._check_samples(samples, threshold, what)
+    M = _samples._check_truths(truths, shape, what)
+    _samples._check_k(shape[0], M, what)
+    K = shape[0] + M
+    return torch.empty((shape[1], shape[2], K, K), dtype=torch.int64, device=samples.device)
+
+
 OPS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "conv_bn_relu", "bn_relu_backward", "bn_finalize",
        "maxpool2d", "maxpool2d_backward", "convT2x2_fwd", "convT2x2_bwd", "upsample_bilinear_ac_fwd",
        "upsample_bilinear_ac_bwd", "attn_gate_fwd", "attn_gate_bwd", "vae_bottleneck_fwd", "vae_bottleneck_bwd",
        "bce_dice_loss", "focal_dice_loss", "seg_counts", "calib_hist", "augment_patch", "clahe", "blur_separable",
        "median_blur", "label_components", "remove_small_components", "distance_transform", "signed_distance",
-       "boundary_loss")
+       "boundary_loss", "sample_gram")
